@@ -2,6 +2,19 @@
 """bench.py - sim-steps/sec of the batched rkFDUpdate hot path on MI355X.
 
   python bench.py --gpus N --steps K --warmup W [--workload config4|config3|config2|config5|config4v|config5v|config1_volume|config4_volume|...] [--batch B]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: it sets up, warms up (W steps), times exactly K steps, writes the
+outputs of the last timed step if --dump-outputs is given, and prints the JSON line (metric, value, unit, ms_per_step,
+config, device status).  --full adds what takes instrumentation or runs of its own: the per-launch roofline (HIP events
+around every launch of the timed steps), the VALU / flop figures, the continuous-trajectory measurement and the CPU
+baselines of the oracle.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step, the arrays a caller of rkfdBatchGetState /
+rkfdBatchGetContact receives, as DIR/<name>.npy in float64: dis, vel, acc [instances, ndof], contact_active and
+contact_force [instances, candidates(, 3)] (with --gpus N > 1: the all-gathered dis and vel).  Above 64 MB in all, a fixed
+seeded sample of instances is written (and its indices as instance_index.npy).  The inputs are seeded: the same arguments
+give the same inputs, so two builds can be compared output for output.
 
 A "step" is one rkFDUpdate (4 RKG stage evaluations + the committing evaluation) of every instance of the
 batch; state stays resident in HBM between steps.
@@ -18,9 +31,9 @@ solved: config.mean_rigid_contacts is read back from the device for exactly the 
 algorithmic bytes are computed from it.  --horizon 0 runs one continuous trajectory instead (the rocking
 regime, ~3.5 contacts; reported in DESIGN.md beside the headline).
 
---steps K is the block that is timed; the block is repeated until the timed region lasts --min-seconds
-(default 6 s) so that the figure does not depend on a 4 ms measurement and a monitor sampling every 5 s sees the GPU busy; ms_per_step and value are averages
-over all timed steps (config.timed_steps), the rollout boundaries continue across blocks.
+--steps K is the number of timed steps (config.timed_steps); the timed steps start at a rollout boundary.  --min-seconds S
+(default 0: off) repeats the block of K steps until the timed region lasts S seconds; ms_per_step and value are averages
+over all timed steps, the rollout boundaries continue across blocks.
 
 One process per GPU; for N>1 the driver launches this file under torch.distributed.run and every rank
 simulates its own shard of instances (no data-path collective; one RCCL all-gather of the final states).
@@ -29,7 +42,7 @@ process, before anything touches the GPU) and relays rank 0's line.
 A step goes out as --split (default 3) launches of the step kernel over contiguous parts of the batch on
 internal HIP streams: the instances are independent, so the thinly occupied tail of one part's step overlaps
 the next step of another (+25 % at 4096 instances per GPU).
-`roofline.kernel_ms` is the average duration of ONE launch (HIP events on the stream it runs on),
+`roofline.kernel_ms` (--full) is the average duration of ONE launch (HIP events on the stream it runs on),
 `roofline.achieved` the algorithmic bytes of one launch over that duration; the launches of a step overlap,
 `achieved_all_launches_of_a_step` relates the whole step's bytes to the step's duration.
 A launch carries --steps-per-launch (default 5) steps of its part of the batch (rkfdBatchSetStepsPerLaunch): the state stays in
@@ -38,7 +51,7 @@ The step kernel is the one compiled for the workload's world (rkfdBatchSpecializ
 in about 2 s; --no-specialize keeps the library's generic kernel; same results either way), with one or two instances per
 wavefront, whichever is faster for that world: --ipw 0 (default) measures both before the timed region
 (rkfdBatchTuneInstancesPerWave; the two give the same bits) and reports the two times.
-Counter-derived fields (roofline.traffic, valu_issue) come from the newest profiles/rNN_* files and only when those carry the
+Counter-derived fields (--full: roofline.traffic, valu_issue) come from the newest profiles/rNN_* files and only when those carry the
 hash of this tree's device sources (else null + the reason).
 Prints ONE JSON line on rank 0.
 """
@@ -194,6 +207,26 @@ def spawn_ranks(args):
     return subprocess.run(cmd, env=env).returncode
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array (instances along axis 0) as <dirname>/<name>.npy in float64; above DUMP_LIMIT_BYTES in all,
+    the same seeded sample of instances from each (the indices as instance_index.npy)"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - 8 * n - 4096) * n // total)      # room for the index and the .npy headers
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["instance_index"] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -203,11 +236,14 @@ def main():
     ap.add_argument("--batch", type=int, default=4096, help="instances per GPU")
     ap.add_argument("--horizon", type=int, default=25, help="steps per rollout before the instances are put back to their start states "
                     "(device-side copy, timed); 0: one continuous trajectory")
-    ap.add_argument("--min-seconds", type=float, default=6.0, help="repeat the --steps block until the timed region lasts this long (6 s: longer "
-                    "than the 5 s sampling period of a utilisation monitor watching the run)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-continuous", action="store_true", help="skip the second, shorter measurement of ONE continuous trajectory per instance "
-                    "(no rollout boundaries; the regime --horizon 0 times), reported as `continuous_trajectory` in the same JSON line")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="repeat the --steps block until the timed region lasts this long (0, the "
+                    "default: time exactly --steps steps)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: per-launch roofline, VALU / flop "
+                    "figures, the continuous trajectory and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-continuous", action="store_true", help="with --full: skip the second, shorter measurement of ONE continuous trajectory "
+                    "per instance (no rollout boundaries; the regime --horizon 0 times), reported as `continuous_trajectory` in the same JSON line")
     ap.add_argument("--fuse", type=int, default=0, help="steps per rkfdBatchUpdate call (0: up to the end of the rollout / block).  Under split "
                     "launches a call of n steps goes out as n rounds of one-step launches, except for worlds under the Vert plugin, whose steps "
                     "run fused in one kernel per part: the QP makes step times vary widely between instances, and without a per-step barrier "
@@ -303,24 +339,27 @@ def main():
 
     run_steps(args.warmup)
     assert b.status(stream) == 0
-    # how many blocks make --min-seconds: one untimed block, the slowest rank decides
-    barrier()
-    t0 = time.perf_counter()
-    run_steps(args.steps)
-    b.join(stream)
-    barrier()
-    t_block = time.perf_counter() - t0
-    reps = max(1, int(np.ceil(args.min_seconds / max(t_block, 1e-6))))
-    if dist is not None:
-        t = torch.tensor([reps], dtype=torch.int64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        reps = int(t.item())
+    reps = 1
+    if args.min_seconds > 0:
+        # how many blocks make --min-seconds: one untimed block, the slowest rank decides
+        barrier()
+        t0 = time.perf_counter()
+        run_steps(args.steps)
+        b.join(stream)
+        barrier()
+        t_block = time.perf_counter() - t0
+        reps = max(1, int(np.ceil(args.min_seconds / max(t_block, 1e-6))))
+        if dist is not None:
+            t = torch.tensor([reps], dtype=torch.int64, device="cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            reps = int(t.item())
     timed_steps = reps * args.steps
     # the timed steps must see the same mix of rollout phases whatever --steps is: start them at a rollout boundary
     if H > 0:
         run_steps(H - pos[0])
     b.contact_stats(reset=True)
-    b.time_launches(True)                     # HIP events around every kernel launch, on the stream it runs on
+    if args.full:
+        b.time_launches(True)                 # HIP events around every kernel launch, on the stream it runs on
 
     ev0 = torch.cuda.Event(enable_timing=True); ev1 = torch.cuda.Event(enable_timing=True)
     barrier()
@@ -335,9 +374,10 @@ def main():
     st = b.status(stream)
     elapsed = t1 - t0
     step_ms = ev0.elapsed_time(ev1) / timed_steps
-    nlaunch, launch_ms = b.launch_timing()
-    assert nlaunch > 0
-    kernel_ms = launch_ms / nlaunch           # average duration of one launch of the step kernel
+    if args.full:
+        nlaunch, launch_ms = b.launch_timing()
+        assert nlaunch > 0
+        kernel_ms = launch_ms / nlaunch       # average duration of one launch of the step kernel
     mean_rg, mean_el, counted = b.contact_stats()
     if sc["world"].model.contents.ncand > 0:       # (worlds without contact candidates keep no contact statistics)
         assert counted == Bn * timed_steps, (counted, Bn, timed_steps)
@@ -352,12 +392,23 @@ def main():
         torch.cuda.synchronize()
         assert out.shape[0] == total
 
+    if args.dump_outputs and rank == 0:
+        if dist is not None:
+            gathered = out.cpu().numpy()
+            dump_outputs(args.dump_outputs, {"dis": gathered[:, :b.ndof], "vel": gathered[:, b.ndof:]})
+        else:
+            outputs = dict(zip(("dis", "vel", "acc"), b.get_state()))
+            if sc["world"].model.contents.ncand > 0:
+                act, _typ, _ref, f = b.get_contact()
+                outputs.update(contact_active=act, contact_force=f)
+            dump_outputs(args.dump_outputs, outputs)
+
     # the same batch on ONE continuous trajectory per instance (what --horizon 0 times): the stiff body leaves the 8-vertex stance
     # after 30-40 steps and rocks on 3-4 vertices (DESIGN.md "Scenario note" - derived with this repository's oracle, not checked
     # against a build of the reference: [UNVERIFIED-DEP]), a lighter contact problem.  Reported beside the headline so that the
     # two regimes can be compared in one line.
     continuous = None
-    if world == 1 and H > 0 and not args.no_continuous:
+    if args.full and world == 1 and H > 0 and not args.no_continuous:
         ncand = sc["world"].model.contents.ncand
         b.set_state(sc["dis"], sc["vel"])
         if ncand > 0:
@@ -371,7 +422,8 @@ def main():
         b.contact_stats(reset=True)
         c0 = torch.cuda.Event(enable_timing=True); c1 = torch.cuda.Event(enable_timing=True)
         tc0 = time.perf_counter(); c0.record()
-        while time.perf_counter() - tc0 < min(1.5, max(args.min_seconds, 0.2)) or cs == 0:
+        cont_s = min(1.5, max(args.min_seconds, 0.2)) if args.min_seconds > 0 else 1.5
+        while time.perf_counter() - tc0 < cont_s or cs == 0:
             b.update(25, stream); cs += 25
             if cs % 200 == 0:
                 b.join(stream); torch.cuda.synchronize()
@@ -387,13 +439,6 @@ def main():
         has_contacts = m.ncand > 0
         if args.workload in ("config4", "config5", "config4v", "config4_26"):
             assert mean_rg > 0, "the timed region solved no rigid contact: the workload is not the one it names"
-        alg, n_fric = alg_bytes(m, mean_rg + mean_el, R)
-        steps_per_launch = 1 if (args.split > 1 and not (args.workload == "config4v")) else None
-        per_launch = Bn // args.split          # instances one launch processes
-        launches_per_step = nlaunch / timed_steps
-        spl = args.split / launches_per_step   # steps one launch carries
-        achieved = alg * per_launch * spl / (kernel_ms * 1e-3) / 1e9
-        traffic, traffic_note = measured_traffic(args.workload, per_launch)
         res = {
             "metric": "sim-steps/sec (node), 30-DoF humanoid + ground contact, batch=4096",
             "value": Bn * world * timed_steps / elapsed, "unit": "sim-steps/sec",
@@ -406,22 +451,28 @@ def main():
                        "mean_rigid_contacts": mean_rg if has_contacts else 0.0, "mean_elastic_contacts": mean_el if has_contacts else 0.0,
                        "parallelism": f"instances sharded over {world} GPU(s), no data-path collective; {args.split} parts of the batch on internal streams, up to {args.steps_per_launch} steps per launch",
                        "step_kernel": ("compiled for this world ahead of time (make spec), loaded from roki-fd_amd/spec" if aot else "compiled for this world at run time (hipRTC)") if specialized else "generic"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
-                         "kernel": "rkfd_step_kernel_spec" if specialized else "rkfd_step_kernel", "kernel_ms": kernel_ms,
-                         "alg_bytes_per_instance_step": alg, "friction_pivot_dofs": n_fric,
-                         "instances_per_launch": per_launch, "launches_per_step": launches_per_step, "steps_per_launch": spl, "step_ms_hip_events": step_ms,
-                         "lds_bytes_per_instance": b.lds_bytes, "resident_instances_per_cu": b.residency(),
-                         "achieved_all_launches_of_a_step": alg * Bn / (step_ms * 1e-3) / 1e9},
             "device_status": st,
         }
+    if rank == 0 and args.full:
+        alg, n_fric = alg_bytes(m, mean_rg + mean_el, R)
+        per_launch = Bn // args.split          # instances one launch processes
+        launches_per_step = nlaunch / timed_steps
+        spl = args.split / launches_per_step   # steps one launch carries
+        achieved = alg * per_launch * spl / (kernel_ms * 1e-3) / 1e9
+        traffic, traffic_note = measured_traffic(args.workload, per_launch)
+        res["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
+                           "kernel": "rkfd_step_kernel_spec" if specialized else "rkfd_step_kernel", "kernel_ms": kernel_ms,
+                           "alg_bytes_per_instance_step": alg, "friction_pivot_dofs": n_fric,
+                           "instances_per_launch": per_launch, "launches_per_step": launches_per_step, "steps_per_launch": spl, "step_ms_hip_events": step_ms,
+                           "lds_bytes_per_instance": b.lds_bytes, "resident_instances_per_cu": b.residency(),
+                           "achieved_all_launches_of_a_step": alg * Bn / (step_ms * 1e-3) / 1e9}
         if continuous is not None:
             res["continuous_trajectory"] = continuous
-        del steps_per_launch
         fl = counted_flops(args.workload, H)
         if fl is not None and args.workload != "config4v":
-            # second axis SURVEY 8d asks for: fp64 vector throughput (dense peak 78.6 TFLOP/s, MI355X_MICROARCH.md).  The flops are
-            # those of the REFERENCE's formulation (counted on the oracle over the same rollout window: link-local ABA, column-probed
+            # second axis SURVEY 8d asks for: fp64 vector throughput (the MI355X's dense fp64 vector peak is 78.6 TFLOP/s).  The flops
+            # are those of the REFERENCE's formulation (counted on the oracle over the same rollout window: link-local ABA, column-probed
             # MLCP), not the device's instruction count - the device's innovations form needs fewer.  Not given for the Vert plugin:
             # the oracle's generic pseudo-inverse KKT solves cost ~10x what the device's structured solve does.
             tf = fl * Bn / (step_ms * 1e-3) / 1e12      # whole step: the launches of one step overlap
@@ -443,6 +494,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:      # the CPU baseline is a single-GPU-run figure (rank 0, N = 1)
             res["cpu_baseline"] = cpu_baseline(R, args.workload, H)
             res["cpu_baseline_all_cores"] = cpu_baseline_all_cores(R, args.workload, H)
+    if rank == 0:
         print(json.dumps(res))
     if dist is not None:
         dist.destroy_process_group()

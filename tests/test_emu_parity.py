@@ -8,6 +8,9 @@ import pytest
 
 from emu import EmuBatch
 
+# the reference's example models, unmodified, kept as data fixtures
+REF_MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_models")
+
 
 @pytest.mark.parametrize("cfg,B,nsteps", [("config2", 2, 2), ("config3", 2, 2), ("config4", 1, 2), ("config1b", 1, 2), ("config5", 1, 1)])
 def test_emulated_kernel_matches_oracle(R, oracle_cls, cfg, B, nsteps):
@@ -129,8 +132,8 @@ def test_emulated_slide_mode_matches_oracle(R, oracle_cls, solver, floor, who):
 @pytest.mark.parametrize("which", ["ball", "shell_humanoid", "mighty"])
 def test_emulated_world_with_more_than_256_candidates(R, oracle_cls, which):
     """the candidate sweep in more than four chunks of 64 (limit 1024, 16-bit contact lists, 12-bit face counts): a
-    tessellated sphere on the floor (274 candidates), the humanoid with six sphere shells (764) and - where the
-    reference checkout is present - the reference's UNMODIFIED mighty.ztk with all its body meshes (749 candidates: its
+    tessellated sphere on the floor (274 candidates), the humanoid with six sphere shells (764) and the
+    reference's UNMODIFIED mighty.ztk with all its body meshes (749 candidates: its
     non-convex shapes' vertices collide with the convex floor; the floor's vertices are not tested against them)"""
     import os
     if which == "ball":
@@ -138,9 +141,7 @@ def test_emulated_world_with_more_than_256_candidates(R, oracle_cls, which):
     elif which == "shell_humanoid":
         sc = R.scenarios.config4_shell(batch=1); nsteps = 2
     else:
-        ref = "/root/reference/example/model/mighty.ztk"
-        if not os.path.exists(ref):
-            pytest.skip("reference checkout not present")
+        ref = os.path.join(REF_MODELS, "mighty.ztk")
         w = R.World(solver=R.SOLVER_MLCP); w.contact_info(os.path.join(R.scenarios.MODELS, "contact_rigid.ztk"))
         h = w.reg_file(ref); w.reg_file(os.path.join(R.scenarios.MODELS, "floor.ztk"))
         w.pair_chain_unreg(h)     # the robot's own pairs off, as the reference's drivers do for an articulated chain (arm_box_test.c:49)
@@ -172,16 +173,14 @@ def test_emulated_spherical_joints(R, oracle_cls, which):
     """spherical joints: on the device a spherical joint is three pseudo-links with revolute joints about the axes of the
     joint-origin frame (three rank-1 eliminations = the rank-3 one), in the oracle a genuine 3-DoF joint with a 3x3
     joint-space inertia - two independent formulations.  models/arm_spher.ztk swinging freely and pressing its hand on
-    the floor (contact paths through the pseudo-links), and - where the reference checkout is present - the
+    the floor (contact paths through the pseudo-links), and the
     reference's own arm.ztk (four spherical joints in series, `COM: auto` / `inertia: auto`; dualarm.ztk gives its
     links no mass - a kinematic model, it loads but has no dynamics to compare)"""
     import os
     if which in ("free", "contact"):
         sc = R.scenarios.arm_spher(batch=2, contact=which == "contact"); nsteps = 2 if which == "contact" else 5
     else:
-        ref = "/root/reference/example/model/arm.ztk"
-        if not os.path.exists(ref):
-            pytest.skip("reference checkout not present")
+        ref = os.path.join(REF_MODELS, "arm.ztk")
         w = R.World(solver=R.SOLVER_MLCP); w.contact_info(os.path.join(R.scenarios.MODELS, "contactinfo.ztk"))
         w.pair_chain_unreg(w.reg_file(ref))           # (alone: with the floor its tessellated spheres and cylinders make 2361 candidates, above the limit of 1024)
         m = w.model.contents
@@ -286,12 +285,11 @@ def test_emulated_volume_humanoid(R, oracle_cls):
     assert np.abs(d[0] - od).max() < 1e-12 and np.abs(v[0] - ov).max() < 1e-10 and np.abs(a[0] - oa).max() / np.abs(oa).max() < 1e-8
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/example/model"), reason="reference checkout not present (it never is on the GPU box)")
 def test_emulated_reference_arm_box_world_under_volume(R, oracle_cls):
     """the world of the reference's arm_box_test.c as that driver sets it up - arm_2DoF.ztk (boxes as polyhedra, two cylinders,
-    a DC motor), box.ztk, floor.ztk read where they lie, rkFDSetSolver( &fd, Volume ): 11 rigid pairs, cylinder - box pairs with
+    a DC motor), box.ztk, floor.ztk (kept under tests/golden/reference_models), rkFDSetSolver( &fd, Volume ): 11 rigid pairs, cylinder - box pairs with
     40 faces; the device tables build and two steps agree with the oracle"""
-    M = "/root/reference/example/model"
+    M = REF_MODELS
     w = R.World(solver=R.SOLVER_VOLUME)
     w.contact_info(os.path.join(M, "contactinfo.ztk"))
     a = w.reg_file(os.path.join(M, "arm_2DoF.ztk")); b = w.reg_file(os.path.join(M, "box.ztk")); w.reg_file(os.path.join(M, "floor.ztk"))

@@ -140,21 +140,18 @@ def test_reference_api_names_in_c(R, tmp_path):
     assert "joint: forearm 0.125" in open(tmp_path / "printed.ztk").read() or "0.125" in open(tmp_path / "printed.ztk").read()
 
 
-REF_MODELS = "/root/reference/example/model"
-REF_DRIVERS = "/root/reference/example/chain"
+# the reference's example models, unmodified, kept as data fixtures
+REF_MODELS = os.path.join(ROOT, "tests", "golden", "reference_models")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DRIVERS), reason="reference checkout not present (it never is on the GPU box)")
-def test_reference_drivers_compile_and_link_unmodified(R, tmp_path):
-    """the reference's five example drivers (read where they lie, not copied) compile with -Werror=implicit-function-declaration
-    against include/roki_fd/roki_fd.h and link against librkfd_amd.so as they are - #include <roki_fd/roki_fd.h>,
-    rkFDODE2Assign( &fd, Regular ), rkFDSetSolver( &fd, Volume ), zVecFreeAtOnce, rkCDPairChainUnreg and all.
-    (They select the Volume plugin, which has a device path for pairs of convex shapes: the worlds of the boxdrop and arm_box
-    drivers are within its limits; arm_wall_test loads wall.ztk, whose breakable-float joint is refused with a message.)"""
+def test_example_drivers_compile_and_link(R, tmp_path):
+    """the drivers in the shape of the reference's example drivers - examples/*.c and tests/c/driver_names.c, which includes
+    <roki_fd/roki_fd.h> as they do and uses the rest of their names (rkFDDT, zRandInit, zVecFPrint, zVecFreeAtOnce, ...) -
+    compile with -Werror=implicit-function-declaration against include/ and link against librkfd_amd.so"""
     import glob
     import subprocess
     root = os.path.join(os.path.dirname(__file__), "..")
-    drivers = sorted(glob.glob(os.path.join(REF_DRIVERS, "*_test.c")))
+    drivers = sorted(glob.glob(os.path.join(root, "examples", "*.c"))) + [os.path.join(root, "tests", "c", "driver_names.c")]
     assert len(drivers) == 5
     for d in drivers:
         exe = str(tmp_path / os.path.basename(d)[:-2])
@@ -163,7 +160,6 @@ def test_reference_drivers_compile_and_link_unmodified(R, tmp_path):
         assert os.path.exists(exe)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference checkout not present (it never is on the GPU box)")
 def test_reader_loads_the_reference_shipped_models(R):
     """the independent ZTK reader against the reference's own example models (read as data): all 12 load - curved
     primitives (sphere / cylinder / cone) as convex polyhedra, `COM: auto` / `inertia: auto` from the shapes,
@@ -288,9 +284,8 @@ def test_specialisation_survives_the_host_changing_its_environment():
     assert r.returncode == 0 and r.stdout.strip().endswith("done"), r.stdout + r.stderr
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference checkout not present (it never is on the GPU box)")
 def test_the_worlds_of_the_reference_drivers_build_device_tables(R):
-    """the worlds the reference's five example drivers set up (example/chain/*_test.c: the models read where they lie, registered
+    """the worlds the reference's five example drivers set up (example/chain/*_test.c: their models, kept under tests/golden/reference_models, registered
     in the drivers' order, rkCDPairChainUnreg where the driver calls it, the plugin the driver selects): the host-side device tables
     build for all five under MLCP / Vert and under the Volume plugin, which the drivers select.  arm_wall_test.c keeps the arm's
     own pairs (no unreg call), among them motor cylinder against motor cylinder: 34 + 34 faces, where the Volume kernel takes one

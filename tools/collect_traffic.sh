@@ -5,15 +5,15 @@
 set -e
 W=${1:-config4}; TAG=${2:-r03}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-OUT=gpurun_out/prof_${TAG}_${W}
+OUT=${OUT_DIR:-out}/prof_${TAG}_${W}
 rm -rf $OUT && mkdir -p $OUT
 # counter passes: the driver's command, but one timed block only (--min-seconds 0): PMC collection serialises the dispatches
 ARGS="bench.py --workload $W --steps 20 --warmup 5 --no-cpu-baseline --min-seconds 0"
 # kernel trace + stats of the SAME command whose JSON line is reported (default steps / warmup), so that
 # the average kernel duration can be compared with bench.py's own HIP-event figure
-# (--no-continuous: the continuous-trajectory record of the default line launches the same kernel on a lighter contact regime,
+# (--min-seconds 6: the timed region of the collection lasts 6 s; --no-continuous: the continuous-trajectory record of the default line launches the same kernel on a lighter contact regime,
 #  which would pull the trace's average below the rollouts' figure; the default line itself is bench_driver_cmd.json)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --workload $W --no-continuous > $OUT.bench.json 2> $OUT.trace.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --min-seconds 6 --workload $W --no-continuous > $OUT.bench.json 2> $OUT.trace.log
 # the counter passes run the lane mapping the traced run chose, without measuring it again: the tuner's launches (both kernels)
 # would otherwise outnumber the timed ones in the per-launch medians
 IPW=$(python3 -c "import json; print(json.loads(open('$OUT.bench.json').read().strip().splitlines()[-1])['config']['instances_per_wavefront'])")
