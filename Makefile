@@ -50,7 +50,7 @@ oracle:
 spec: $(LIB)
 	python3 tools/make_spec.py
 
-emu: tests/emu/librkfd_emu.so tests/emu/librkfd_emu_w2.so
+emu: tests/emu/librkfd_emu.so tests/emu/librkfd_emu_w2.so tests/emu/librkfd_emu_ctrl.so tests/emu/librkfd_emu_ctrl_w2.so
 
 tests/emu/librkfd_emu.so: tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_device.h $(CSRC)/rkfd_devmodel.cpp $(CSRC)/*.h $(CSRC)/device/*.h include/*.h
 	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread $(INC) -o $@ tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_devmodel.cpp
@@ -59,8 +59,15 @@ tests/emu/librkfd_emu.so: tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_device.h $(CSRC)/r
 tests/emu/librkfd_emu_w2.so: tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_device.h $(CSRC)/rkfd_devmodel.cpp $(CSRC)/*.h $(CSRC)/device/*.h include/*.h
 	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread -DRKFD_W=2 $(INC) -o $@ tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_devmodel.cpp
 
+# the harness with control schedules (rkfdBatchUpdateControlled's launches), one and two instances per wavefront
+tests/emu/librkfd_emu_ctrl.so: tests/emu/rkfd_emu_ctrl.cpp tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_device.h $(CSRC)/rkfd_devmodel.cpp $(CSRC)/*.h $(CSRC)/device/*.h include/*.h
+	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread $(INC) -o $@ tests/emu/rkfd_emu_ctrl.cpp $(CSRC)/rkfd_devmodel.cpp
+
+tests/emu/librkfd_emu_ctrl_w2.so: tests/emu/rkfd_emu_ctrl.cpp tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_device.h $(CSRC)/rkfd_devmodel.cpp $(CSRC)/*.h $(CSRC)/device/*.h include/*.h
+	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread -DRKFD_W=2 $(INC) -o $@ tests/emu/rkfd_emu_ctrl.cpp $(CSRC)/rkfd_devmodel.cpp
+
 clean:
-	rm -rf $(BUILD) $(LIB) $(PKG)/spec tests/emu/librkfd_emu.so tests/emu/librkfd_emu_w2.so
+	rm -rf $(BUILD) $(LIB) $(PKG)/spec tests/emu/librkfd_emu.so tests/emu/librkfd_emu_w2.so tests/emu/librkfd_emu_ctrl.so tests/emu/librkfd_emu_ctrl_w2.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle emu spec clean

@@ -71,6 +71,16 @@ int rkfdBatchUpdateInit(rkfdBatch *b, void *stream);
 /* nsteps x rkFDUpdate (reference src/rkfd_sim.c:560-566) for every instance: one launch with the steps fused, or -
  * under split launches - nsteps rounds of one-step launches on the internal streams (same results).  Asynchronous. */
 int rkfdBatchUpdate(rkfdBatch *b, int nsteps, void *stream);
+/* nsteps x ( rkJointMotorSetInput on every link; rkFDUpdate ) - the reference drivers' control loop (example/chain/arm_box_test.c:
+ * 16-21,69-82) - with the motor inputs of a control schedule u[batch][nsteps][nlink] (instance-major: u[(b*nsteps + k)*nlink + l] is
+ * the input of link l in step k of instance b).  Bit-identical to nsteps x ( rkfdBatchSetMotorInput( u[:, k, :] );
+ * rkfdBatchUpdate( 1 ) ), in the launches rkfdBatchUpdate makes; afterwards the batch's motor input is the last row u[:, nsteps-1, :].
+ * Host schedule: copied into a buffer of the batch before the call returns (u may be reused at once), then to the device in stream
+ * order.  Asynchronous. */
+int rkfdBatchUpdateControlled(rkfdBatch *b, int nsteps, const double *u, void *stream);
+/* the same with the schedule on the batch's device, read in stream order after `stream` (no copy: schedules sampled on the GPU);
+ * the caller keeps u_dev unchanged until the steps are done (rkfdBatchJoin on a stream it then orders by, or rkfdBatchStatus) */
+int rkfdBatchUpdateControlledDev(rkfdBatch *b, int nsteps, const double *u_dev, void *stream);
 /* one evaluation _rkFDUpdate (doUpRef=0) or _rkFDUpdateRef (doUpRef=1) at the current state
  * (reference src/rkfd_sim.c:533-549): fills acc and the contact forces.  Asynchronous. */
 int rkfdBatchEval(rkfdBatch *b, int doUpRef, void *stream);
@@ -208,6 +218,9 @@ int rkfdNodeUpdate(rkfdNode *n, int nsteps);
 int rkfdNodeSnapshot(rkfdNode *n);
 int rkfdNodeRestore(rkfdNode *n);
 int rkfdNodeStatus(rkfdNode *n);
+/* rkfdBatchUpdateControlled on every device: u is the host schedule of ALL instances, [total][nsteps][nlink]; each device's thread
+ * copies its shard's contiguous block on the device's own stream, in order with its steps */
+int rkfdNodeUpdateControlled(rkfdNode *n, int nsteps, const double *u);
 /* one ncclAllGather of the final {dis, vel}: afterwards every device holds all `total` final states (rkfdNodeGatherDev: on
  * device k, [ndev][mx][2 ndof] doubles - block j = shard j's instances, dis | vel per instance, padded to the largest shard mx),
  * and dis / vel ([total][ndof], either may be NULL) receive them on the host in instance order */

@@ -100,6 +100,8 @@ def lib():
     L.rkfdBatchUpdateInit.argtypes = [vp, vp]
     L.rkfdBatchUpdate.argtypes = [vp, C.c_int, vp]
     L.rkfdBatchEval.argtypes = [vp, C.c_int, vp]
+    L.rkfdBatchUpdateControlled.argtypes = [vp, C.c_int, vp, vp]; L.rkfdBatchUpdateControlledDev.argtypes = [vp, C.c_int, vp, vp]
+    L.rkfdNodeUpdateControlled.argtypes = [vp, C.c_int, vp]
     L.rkfdLdsBytesFor.argtypes = [C.POINTER(RkfdModel), C.c_int]
     L.rkfdBatchStatus.argtypes = [vp, vp]
     L.rkfdBatchContactStats.argtypes = [vp, C.c_int, _pd, _pd, C.POINTER(C.c_longlong)]
@@ -209,6 +211,8 @@ class Batch:
         self.world = world
         m = world.model.contents
         self.B, self.ndof, self.nlink, self.ncand = batch, m.ndof, m.nlink, m.ncand
+        self.device = device
+        self._ctrl_keep = []           # device schedules of update_controlled() the launches issued since the last join / sync read
         self._b = self._L.rkfdBatchCreate(world.model, batch, device, max_rigid)
         if not self._b:
             raise RkfdError(self._L.rkfdHipLastError().decode())
@@ -228,49 +232,54 @@ class Batch:
         if r < 0:
             raise RkfdError(self._L.rkfdHipLastError().decode())
 
+    def _synced(self, r):
+        """after a call that waited for the batch's launches: the device schedules they read may go"""
+        self._chk(r)
+        self._ctrl_keep.clear()
+
     def set_state(self, dis, vel):
         dis = np.ascontiguousarray(dis, dtype=np.float64).reshape(self.B, self.ndof)
         vel = np.ascontiguousarray(vel, dtype=np.float64).reshape(self.B, self.ndof)
-        self._chk(self._L.rkfdBatchSetState(self._b, _ptr(dis), _ptr(vel)))
+        self._synced(self._L.rkfdBatchSetState(self._b, _ptr(dis), _ptr(vel)))
 
     def get_state(self):
         dis = np.empty((self.B, self.ndof)); vel = np.empty_like(dis); acc = np.empty_like(dis)
-        self._chk(self._L.rkfdBatchGetState(self._b, _ptr(dis), _ptr(vel), _ptr(acc)))
+        self._synced(self._L.rkfdBatchGetState(self._b, _ptr(dis), _ptr(vel), _ptr(acc)))
         return dis, vel, acc
 
     def set_motor_input(self, inp):
         inp = np.ascontiguousarray(inp, dtype=np.float64).reshape(self.B, self.nlink)
-        self._chk(self._L.rkfdBatchSetMotorInput(self._b, _ptr(inp)))
+        self._synced(self._L.rkfdBatchSetMotorInput(self._b, _ptr(inp)))
 
     def get_contact(self):
         act = np.empty((self.B, self.ncand), dtype=np.int32); typ = np.empty_like(act)
         ref = np.empty((self.B, self.ncand, 3)); f = np.empty_like(ref)
-        self._chk(self._L.rkfdBatchGetContact(self._b, _ptr(act), _ptr(typ), _ptr(ref), _ptr(f)))
+        self._synced(self._L.rkfdBatchGetContact(self._b, _ptr(act), _ptr(typ), _ptr(ref), _ptr(f)))
         return act, typ, ref, f
 
     def set_contact(self, act, typ, ref):
         act = np.ascontiguousarray(act, dtype=np.int32); typ = np.ascontiguousarray(typ, dtype=np.int32)
         ref = np.ascontiguousarray(ref, dtype=np.float64)
-        self._chk(self._L.rkfdBatchSetContact(self._b, _ptr(act), _ptr(typ), _ptr(ref)))
+        self._synced(self._L.rkfdBatchSetContact(self._b, _ptr(act), _ptr(typ), _ptr(ref)))
 
     def get_pivot(self):
         typ = np.empty((self.B, self.nlink), dtype=np.int32); prev = np.empty((self.B, self.nlink))
-        self._chk(self._L.rkfdBatchGetPivot(self._b, _ptr(typ), _ptr(prev)))
+        self._synced(self._L.rkfdBatchGetPivot(self._b, _ptr(typ), _ptr(prev)))
         return typ, prev
 
     def set_pivot(self, typ, prev):
         typ = np.ascontiguousarray(typ, dtype=np.int32); prev = np.ascontiguousarray(prev, dtype=np.float64)
-        self._chk(self._L.rkfdBatchSetPivot(self._b, _ptr(typ), _ptr(prev)))
+        self._synced(self._L.rkfdBatchSetPivot(self._b, _ptr(typ), _ptr(prev)))
 
     def get_broken(self):
         """breakable float joints: 1 per link whose joint has broken, [B, nlink]"""
         br = np.empty((self.B, self.nlink), dtype=np.int32)
-        self._chk(self._L.rkfdBatchGetBroken(self._b, _ptr(br)))
+        self._synced(self._L.rkfdBatchGetBroken(self._b, _ptr(br)))
         return br
 
     def set_broken(self, broken):
         br = np.ascontiguousarray(broken, dtype=np.int32).reshape(self.B, self.nlink)
-        self._chk(self._L.rkfdBatchSetBroken(self._b, _ptr(br)))
+        self._synced(self._L.rkfdBatchSetBroken(self._b, _ptr(br)))
 
     def update_init(self, stream=None):
         self._chk(self._L.rkfdBatchUpdateInit(self._b, stream))
@@ -278,13 +287,41 @@ class Batch:
     def update(self, nsteps=1, stream=None):
         self._chk(self._L.rkfdBatchUpdate(self._b, nsteps, stream))
 
+    def update_controlled(self, u, stream=None):
+        """H x (set the motor inputs u[:, k, :]; rkFDUpdate) for a control schedule u of shape (B, H, nlink), float64: the same bits as
+        H x (set_motor_input(u[:, k]); update(1)), in the launches update() makes; afterwards the motor input is u[:, H-1, :].
+        A numpy array is copied before the call returns.  A torch tensor on the batch's device is read in place, in order after
+        `stream` (default: torch.cuda.current_stream()); the batch keeps a reference to it until join() or a synchronous accessor."""
+        if isinstance(u, np.ndarray):
+            if u.ndim != 3 or u.shape[0] != self.B or u.shape[2] != self.nlink or u.shape[1] < 1:
+                raise ValueError(f"control schedule of shape {u.shape}: expected ({self.B}, H, {self.nlink})")
+            if u.dtype != np.float64:
+                raise TypeError(f"control schedule of dtype {u.dtype}: expected float64")
+            u = np.ascontiguousarray(u)
+            self._chk(self._L.rkfdBatchUpdateControlled(self._b, u.shape[1], _ptr(u), stream))
+            return
+        import torch
+        if not isinstance(u, torch.Tensor):
+            raise TypeError(f"control schedule of type {type(u).__name__}: expected a numpy array or a torch tensor")
+        if u.dim() != 3 or u.shape[0] != self.B or u.shape[2] != self.nlink or u.shape[1] < 1:
+            raise ValueError(f"control schedule of shape {tuple(u.shape)}: expected ({self.B}, H, {self.nlink})")
+        if u.dtype != torch.float64:
+            raise TypeError(f"control schedule of dtype {u.dtype}: expected torch.float64")
+        if u.device.type != "cuda" or u.device.index != self.device:
+            raise ValueError(f"control schedule on {u.device}: expected cuda:{self.device}")
+        if not u.is_contiguous():
+            raise ValueError("control schedule: the tensor must be contiguous")
+        if stream is None:
+            stream = torch.cuda.current_stream(u.device).cuda_stream
+        self._chk(self._L.rkfdBatchUpdateControlledDev(self._b, u.shape[1], C.c_void_p(u.data_ptr()), C.c_void_p(stream or 0)))
+        self._ctrl_keep.append(u)      # read by launches that may still be queued on the internal streams
+
     def eval(self, do_up_ref=False, stream=None):
         self._chk(self._L.rkfdBatchEval(self._b, 1 if do_up_ref else 0, stream))
 
     def status(self, stream=None):
         r = self._L.rkfdBatchStatus(self._b, stream)
-        if r < 0:
-            raise RkfdError(self._L.rkfdHipLastError().decode())
+        self._synced(r)
         return r
 
     def contact_stats(self, reset=False):
@@ -307,7 +344,7 @@ class Batch:
 
     def join(self, stream=None):
         """rkfdBatchJoin: make `stream` wait for the split launches (no host synchronisation)"""
-        self._chk(self._L.rkfdBatchJoin(self._b, C.c_void_p(stream or 0)))
+        self._synced(self._L.rkfdBatchJoin(self._b, C.c_void_p(stream or 0)))
 
     def time_launches(self, on=True):
         self._chk(self._L.rkfdBatchTimeLaunches(self._b, int(bool(on))))
@@ -418,6 +455,15 @@ class Node:
     def set_motor_input(self, inp):
         inp = np.ascontiguousarray(inp, dtype=np.float64).reshape(self.total, self.nlink)
         self._chk(self._L.rkfdNodeSetMotorInput(self._n, _ptr(inp)))
+
+    def update_controlled(self, u):
+        """Batch.update_controlled on every device: u is the host schedule of all instances, (total, H, nlink) float64"""
+        if not isinstance(u, np.ndarray) or u.ndim != 3 or u.shape[0] != self.total or u.shape[2] != self.nlink or u.shape[1] < 1:
+            raise ValueError(f"control schedule of shape {getattr(u, 'shape', None)}: expected a numpy array ({self.total}, H, {self.nlink})")
+        if u.dtype != np.float64:
+            raise TypeError(f"control schedule of dtype {u.dtype}: expected float64")
+        u = np.ascontiguousarray(u)
+        self._chk(self._L.rkfdNodeUpdateControlled(self._n, u.shape[1], _ptr(u)))
 
     def get_state(self):
         dis = np.empty((self.total, self.ndof)); vel = np.empty_like(dis); acc = np.empty_like(dis)

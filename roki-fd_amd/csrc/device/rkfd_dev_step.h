@@ -133,8 +133,13 @@ RKFD_DEV void rkfd_cat_dis(const rkfdDevModel &m, const rkfdLds &L, int dofkind,
 /* The instance of this lane: with RKFD_W instances per wavefront, half h of workgroup wg simulates instance first + wg RKFD_W + h
  * and owns the h-th block of lds_instance bytes of the workgroup's LDS.  A half beyond the end of the batch part (odd count) keeps
  * in step by simulating the instance before it once more - the halves share every branch and barrier - and stores nothing. */
+/* ctrl (mode 0 only; NULL: the motor input of st.motor_in holds for the whole launch): a control schedule, ctrl[b*ctrl_stride +
+ * s*nlink_model + model link] is the motor input of step s of this launch - rkJointMotorSetInput before each rkFDUpdate.  It holds
+ * for the four Runge-Kutta-Gill stages and the committing evaluation of its step; the last step's input is stored to st.motor_in
+ * (for the model links the device simulates - a link merged into its parent has no motor the device reads). */
 template<bool prof, int vqp, bool pk> RKFD_DEV void rkfd_instance(const rkfdDevModel &m_, const rkfdDevState &st, int b, void *ldsbase,
-                            int mode, int nsteps, int *errflag, bool live = true, void *ldsshared = 0)
+                            int mode, int nsteps, int *errflag, bool live = true, void *ldsshared = 0,
+                            const double *ctrl = nullptr, int ctrl_stride = 0)
 {
 #ifdef RKFD_SPEC
   /* kernel compiled for ONE world (rkfdBatchSpecialize, hipRTC): its dimensions are literals, so the LDS layout,
@@ -252,6 +257,9 @@ template<bool prof, int vqp, bool pk> RKFD_DEV void rkfd_instance(const rkfdDevM
       const double k = stage == 1 ? 0.5*h : ( stage == 4 ? h/6.0 : h );
       const double xv = ( mode == 0 && stage > 0 ) ? fma( k, Ta, qd ) : qd;
       if( stage == 0 ){
+        /* this step's motor input (ctrl has been advanced to the step's row; the per-lane offset is recomputed here: nothing 64-bit
+         * per lane lives across the step loop) */
+        if( ctrl && mode == 0 && lane < NL ) ll.min = ctrl[(size_t)b*ctrl_stride + m.orig[lane]];
         if( on ) L.q[lane] = q;
         SYNC();
       } else {
@@ -272,7 +280,8 @@ template<bool prof, int vqp, bool pk> RKFD_DEV void rkfd_instance(const rkfdDevM
       else if( stage == 2 ){ Fv = fma( w3, xv, Fv ); Fa = fma( w3, a, Fa ); Tv = fma( c32, xv, Pv ); Ta = fma( c32, a, Pa ); }
       else if( stage == 3 ){ Fv += xv; Fa += a; Tv = Fv; Ta = Fa; }
       SYNC();
-      stage++; if( stage == nst ) stage = 0;
+      stage++;
+      if( stage == nst ){ stage = 0; if( ctrl ) ctrl += m.nlink_model; }
     }
   }
   if( prof && live && lane == 0 && st.prof ){
@@ -291,6 +300,7 @@ template<bool prof, int vqp, bool pk> RKFD_DEV void rkfd_instance(const rkfdDevM
     const int lm = m.orig[lane];
     st.piv_type[(size_t)b*m.nlink_model+lm] = ll.pivt;
     st.piv_prev[(size_t)b*m.nlink_model+lm] = ll.pivp;
+    if( ctrl && mode == 0 ) st.motor_in[(size_t)b*m.nlink_model+lm] = ll.min;      /* the input persists, as rkJointMotorSetInput's */
   }
   if( m.has_brf && live ) rkfd_brf_store( m, st, L, b );
   /* contact state: the flag of every candidate, the rest only for those in contact (a candidate out of

@@ -31,12 +31,12 @@ static thread_local char g_err[512] = "";
  * constants) and addresses out of the step loop and the kernels need 184-193. */
 #define RKFD_KERNEL(name, prof, vqp, pk, waves) \
 extern "C" __global__ void __launch_bounds__(RKFD_WAVE, waves) \
-name(rkfdDevModel m, rkfdDevState st, int first, int mode, int nsteps, int *errflag) \
+name(rkfdDevModel m, rkfdDevState st, int first, int mode, int nsteps, int *errflag, const double *ctrl, int ctrl_stride) \
 { \
   extern __shared__ __attribute__((aligned(16))) char lds[]; \
   const int b = first + (int)blockIdx.x; \
   if( b >= st.batch ) return; \
-  rkfd_instance<prof, vqp, pk>( m, st, b, lds, mode, nsteps, errflag ); \
+  rkfd_instance<prof, vqp, pk>( m, st, b, lds, mode, nsteps, errflag, true, 0, prof ? nullptr : ctrl, ctrl_stride ); \
 }
 RKFD_KERNEL( rkfd_step_kernel, false, 0, false, 3 )
 /* the contact matrix as a packed lower triangle (worlds where that lets one more instance share a CU) */
@@ -46,7 +46,8 @@ RKFD_KERNEL( rkfd_step_kernel_pk, false, 0, true, 3 )
 /* (two waves per SIMD: up to 24 unknowns the QP keeps the factor of its Q in registers - 96 of them - and the QP's LDS allows at
  *  most eight instances per CU anyway) */
 RKFD_KERNEL( rkfd_step_kernel_vqp, false, 1, false, 2 )
-/* diagnostic instantiations with in-kernel phase stamps (rkfdBatchProfile) */
+/* diagnostic instantiations with in-kernel phase stamps (rkfdBatchProfile); they never carry a control schedule (the profile steps
+ * with the batch's motor input), so they drop it and keep their registers */
 RKFD_KERNEL( rkfd_step_kernel_prof, true, 0, false, 3 )
 RKFD_KERNEL( rkfd_step_kernel_prof_pk, true, 0, true, 3 )
 RKFD_KERNEL( rkfd_step_kernel_prof_vqp, true, 1, false, 2 )
@@ -55,20 +56,20 @@ RKFD_KERNEL( rkfd_step_kernel_prof_vqp, true, 1, false, 2 )
  * ~90 vector registers it spills (measured, box on the floor / humanoid on two soles, M steps/s: one wave 2.33 / 1.49, two
  * 4.55 / 1.68, three 4.47 / 1.41 - the humanoid's 32 KB of LDS allow five instances per CU either way) */
 extern "C" __global__ void __launch_bounds__(RKFD_WAVE, 2)
-rkfd_step_kernel_vol(rkfdDevModel m, rkfdDevState st, int first, int mode, int nsteps, int *errflag)
+rkfd_step_kernel_vol(rkfdDevModel m, rkfdDevState st, int first, int mode, int nsteps, int *errflag, const double *ctrl, int ctrl_stride)
 {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int b = first + (int)blockIdx.x;
   if( b >= st.batch ) return;
-  rkfd_instance<false, 2, false>( m, st, b, lds, mode, nsteps, errflag );
+  rkfd_instance<false, 2, false>( m, st, b, lds, mode, nsteps, errflag, true, 0, ctrl, ctrl_stride );
 }
 extern "C" __global__ void __launch_bounds__(RKFD_WAVE, 2)
-rkfd_step_kernel_prof_vol(rkfdDevModel m, rkfdDevState st, int first, int mode, int nsteps, int *errflag)
+rkfd_step_kernel_prof_vol(rkfdDevModel m, rkfdDevState st, int first, int mode, int nsteps, int *errflag, const double *ctrl, int ctrl_stride)
 {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int b = first + (int)blockIdx.x;
   if( b >= st.batch ) return;
-  rkfd_instance<true, 2, false>( m, st, b, lds, mode, nsteps, errflag );
+  rkfd_instance<true, 2, false>( m, st, b, lds, mode, nsteps, errflag, true, 0, nullptr, ctrl_stride );
 }
 
 /* rkfdBatchRestore: one workgroup copies one instance's state rows back from the snapshot */
@@ -92,7 +93,7 @@ rkfd_restore_kernel(rkfdDevState st, rkfdDevState sn, int first, int ND, int NLM
   }
 }
 
-typedef void (*rkfdKernel)(rkfdDevModel, rkfdDevState, int, int, int, int *);
+typedef void (*rkfdKernel)(rkfdDevModel, rkfdDevState, int, int, int, int *, const double *, int);
 #define RKFD_MAX_SPLIT 8
 
 struct rkfdBatch {
@@ -127,6 +128,13 @@ struct rkfdBatch {
   int timing;
   std::vector<hipEvent_t> *tev;      /* pool of pre-created events; start / stop pairs occupy [0, tused) */
   size_t tused;
+  /* rkfdBatchUpdateControlled: the schedule's device copy and its pinned host staging (grown on demand); every part copies its own
+   * block on the stream it steps on, and ctrl_ev[k] marks the end of part k's copy: the next call waits for them before it
+   * overwrites the staging */
+  double *d_ctrl, *h_ctrl;
+  size_t ctrl_cap;                   /* doubles */
+  hipEvent_t ctrl_ev[RKFD_MAX_SPLIT];
+  int ctrl_nev;                      /* events of ctrl_ev recorded by the last call */
 };
 
 extern "C" const char *rkfdHipLastError(void){ return g_err; }
@@ -223,6 +231,9 @@ extern "C" void rkfdBatchDestroy(rkfdBatch *b)
     for( int k=0; k<RKFD_MAX_SPLIT; k++ ){ (void)hipStreamSynchronize( b->sub[k] ); (void)hipStreamDestroy( b->sub[k] ); (void)hipEventDestroy( b->done[k] ); }
   }
   if( b->tev ){ for( size_t i=0; i<b->tev->size(); i++ ) (void)hipEventDestroy( (*b->tev)[i] ); delete b->tev; }
+  for( int k=0; k<b->ctrl_nev; k++ ) (void)hipEventSynchronize( b->ctrl_ev[k] );
+  for( int k=0; k<RKFD_MAX_SPLIT; k++ ) if( b->ctrl_ev[k] ) (void)hipEventDestroy( b->ctrl_ev[k] );
+  (void)hipFree( b->d_ctrl ); if( b->h_ctrl ) (void)hipHostFree( b->h_ctrl );
   if( b->spec_mod ) (void)hipModuleUnload( b->spec_mod );
   (void)hipFree( b->d_err ); (void)hipFree( b->dblob ); (void)hipFree( b->dblob2 );
   rkfd_devmodel_free( &b->host ); rkfd_devmodel_free( &b->host2 );
@@ -403,7 +414,9 @@ static int sync_streams(rkfdBatch *b)
   return 0;
 }
 /* one kernel launch over `count` instances starting at `first`: the kernel compiled for this world when there is one */
-static int launch_one(rkfdBatch *b, rkfdKernel kern, int count, int first, int mode, int nsteps, hipStream_t stream)
+/* ctrl / ctrl_stride: the control schedule of this launch's first step (NULL: the motor input in the state holds) */
+static int launch_one(rkfdBatch *b, rkfdKernel kern, int count, int first, int mode, int nsteps, hipStream_t stream,
+                      const double *ctrl = NULL, int ctrl_stride = 0)
 {
   if( b->spec_fn && !b->st.prof ){
     if( b->ipw == 2 ){
@@ -411,29 +424,43 @@ static int launch_one(rkfdBatch *b, rkfdKernel kern, int count, int first, int m
        * part ends through st.batch (a half beyond it is a stand-in that stores nothing) */
       rkfdDevState st2 = b->st;
       st2.batch = first + count;
-      void *args[] = { &b->dm2, &st2, &first, &mode, &nsteps, &b->d_err };
+      void *args[] = { &b->dm2, &st2, &first, &mode, &nsteps, &b->d_err, &ctrl, &ctrl_stride };
       HIPCHK( hipModuleLaunchKernel( b->spec_fn, ( count+1 )/2, 1, 1, RKFD_WAVE, 1, 1, (unsigned)( 2*b->host2.lds_bytes + (size_t)b->host2.dm.lds_shared ), stream, args, NULL ), -1 );
       return 0;
     }
-    void *args[] = { &b->dm, &b->st, &first, &mode, &nsteps, &b->d_err };
+    void *args[] = { &b->dm, &b->st, &first, &mode, &nsteps, &b->d_err, &ctrl, &ctrl_stride };
     HIPCHK( hipModuleLaunchKernel( b->spec_fn, count, 1, 1, RKFD_WAVE, 1, 1, (unsigned)b->lds_bytes, stream, args, NULL ), -1 );
     return 0;
   }
-  hipLaunchKernelGGL( kern, dim3( count ), dim3( RKFD_WAVE ), b->lds_bytes, stream, b->dm, b->st, first, mode, nsteps, b->d_err );
+  hipLaunchKernelGGL( kern, dim3( count ), dim3( RKFD_WAVE ), b->lds_bytes, stream, b->dm, b->st, first, mode, nsteps, b->d_err, ctrl, ctrl_stride );
   HIPCHK( hipGetLastError(), -1 );
   return 0;
 }
 
-static int launch(rkfdBatch *b, int mode, int nsteps, void *stream)
+/* the host schedule's block of instances [lo, hi) from the pinned staging into the device copy, on the stream that steps them;
+ * ctrl_ev[ev] marks its end */
+static int ctrl_upload(rkfdBatch *b, int lo, int hi, int nsteps, hipStream_t s, int ev)
+{
+  const size_t row = (size_t)nsteps*b->nlink, off = (size_t)lo*row;
+  HIPCHK( hipMemcpyAsync( b->d_ctrl + off, b->h_ctrl + off, sizeof(double)*row*(size_t)( hi-lo ), hipMemcpyHostToDevice, s ), -1 );
+  HIPCHK( hipEventRecord( b->ctrl_ev[ev], s ), -1 );
+  if( ev + 1 > b->ctrl_nev ) b->ctrl_nev = ev + 1;
+  return 0;
+}
+/* ctrl: NULL, or a control schedule [batch][nsteps][nlink] on the device (mode 0); upload: it is the batch's own copy, and every
+ * part first brings its block over from the pinned staging (ctrl_upload) */
+static int launch(rkfdBatch *b, int mode, int nsteps, void *stream, const double *ctrl = NULL, bool upload = false)
 {
   if( !b ){ SETERR( "null batch" ); return -1; }
   HIPCHK( hipSetDevice( b->device ), -1 );
   rkfdKernel kern = b->st.prof ? b->kern_prof : b->kern;
+  const int cstride = ctrl ? nsteps*b->nlink : 0;
   if( b->nsplit <= 1 || b->st.prof ){
     if( b->st.prof && sync_streams( b ) < 0 ) return -1;
+    if( upload && ctrl_upload( b, 0, b->batch, nsteps, (hipStream_t)stream, 0 ) < 0 ) return -1;
     hipEvent_t e0 = NULL, e1 = NULL;
     if( b->timing && !b->st.prof && timing_pair( b, &e0, &e1 ) ) HIPCHK( hipEventRecord( e0, (hipStream_t)stream ), -1 );
-    if( launch_one( b, kern, b->batch, 0, mode, nsteps, (hipStream_t)stream ) < 0 ) return -1;
+    if( launch_one( b, kern, b->batch, 0, mode, nsteps, (hipStream_t)stream, ctrl, cstride ) < 0 ) return -1;
     if( e0 && e1 ) HIPCHK( hipEventRecord( e1, (hipStream_t)stream ), -1 );
     return 0;
   }
@@ -455,9 +482,13 @@ static int launch(rkfdBatch *b, int mode, int nsteps, void *stream)
     for( int k=0; k<b->nsplit; k++ ){
       const int lo = (int)( (long long)b->batch*k/b->nsplit ), hi = (int)( (long long)b->batch*( k+1 )/b->nsplit );
       if( hi <= lo ) continue;
+      /* (the part's block of the batch's copy is read by this part only: its upload waits for nothing but its own earlier steps) */
+      if( upload && r == 0 && ctrl_upload( b, lo, hi, nsteps, b->sub[k], k ) < 0 ) return -1;
       hipEvent_t e0 = NULL, e1 = NULL;
       if( b->timing && timing_pair( b, &e0, &e1 ) ) HIPCHK( hipEventRecord( e0, b->sub[k] ), -1 );
-      if( launch_one( b, kern, hi-lo, lo, mode, ( r+1 )*per <= nsteps ? per : nsteps - r*per, b->sub[k] ) < 0 ) return -1;
+      /* round r starts at step r per of the schedule; the stride of an instance stays that of the whole schedule */
+      if( launch_one( b, kern, hi-lo, lo, mode, ( r+1 )*per <= nsteps ? per : nsteps - r*per, b->sub[k],
+                      ctrl ? ctrl + (size_t)r*per*b->nlink : NULL, cstride ) < 0 ) return -1;
       if( e0 && e1 ) HIPCHK( hipEventRecord( e1, b->sub[k] ), -1 );
     }
   for( int k=0; k<b->nsplit; k++ ) HIPCHK( hipEventRecord( b->done[k], b->sub[k] ), -1 );
@@ -481,14 +512,14 @@ static std::string spec_source(const rkfdDevModel &d, int ipw = 1)
     "#define RKFD_SPEC_VOL_NPAIR %d\n#define RKFD_SPEC_VOL_NP %d\n#define RKFD_SPEC_VOL_NCP %d\n#define RKFD_SPEC_VOL_PV %d\n#define RKFD_SPEC_VOL_NF %d\n"
     "#include \"rkfd_device.h\"\n"
     "extern \"C\" __global__ void __launch_bounds__(64, %d)\n"
-    "rkfd_step_kernel_spec(rkfdDevModel m, rkfdDevState st, int first, int mode, int nsteps, int *errflag)\n"
+    "rkfd_step_kernel_spec(rkfdDevModel m, rkfdDevState st, int first, int mode, int nsteps, int *errflag, const double *ctrl, int ctrl_stride)\n"
     "{\n"
     "  extern __shared__ __attribute__((aligned(16))) char lds[];\n"
     "  int b = first + (int)blockIdx.x*RKFD_W + HALF();\n"
     "  if( RKFD_W == 1 && b >= st.batch ) return;\n"
     "  const bool live = b < st.batch;\n"
     "  if( !live ) b -= 1;\n"
-    "  rkfd_instance<false, %s, %s>( m, st, b, lds + HALF()*RKFD_SPEC_LDS_INSTANCE, mode, nsteps, errflag, live, lds + RKFD_W*RKFD_SPEC_LDS_INSTANCE );\n"
+    "  rkfd_instance<false, %s, %s>( m, st, b, lds + HALF()*RKFD_SPEC_LDS_INSTANCE, mode, nsteps, errflag, live, lds + RKFD_W*RKFD_SPEC_LDS_INSTANCE, ctrl, ctrl_stride );\n"
     "}\n",
     ipw, d.nlink, d.ndof, d.ncand, d.nlink_model, d.nlevel, d.nround, d.nsched, d.maxrg, d.npool, d.nfloat, d.maxact, d.nside,
     d.npurow, d.pu_d0, d.pu_alias, d.vert_rigid, d.qscr_alias, d.has_slide, d.ma_size, d.ma_packed, d.max_iter, d.solver, d.pyramid, d.anchor, d.mlcp_mfma,
@@ -876,6 +907,41 @@ extern "C" int rkfdBatchUpdate(rkfdBatch *b, int nsteps, void *stream)
   return launch( b, 0, nsteps, stream );
 }
 extern "C" int rkfdBatchEval(rkfdBatch *b, int doUpRef, void *stream){ return launch( b, doUpRef ? 1 : 2, 0, stream ); }
+
+/* nsteps x ( rkJointMotorSetInput; rkFDUpdate ) with the inputs of a control schedule u[batch][nsteps][nlink]: the same bits as
+ * nsteps x ( rkfdBatchSetMotorInput( u[:, k, :] ); rkfdBatchUpdate( 1 ) ), in the launches rkfdBatchUpdate makes (split parts,
+ * steps per launch, the world-specific kernel).  Host schedule: copied into pinned staging before the call returns, then to the
+ * batch's device copy in stream order. */
+extern "C" int rkfdBatchUpdateControlled(rkfdBatch *b, int nsteps, const double *u, void *stream)
+{
+  if( !b || !u || nsteps < 1 ){ SETERR( "rkfdBatchUpdateControlled: %s", !b ? "null batch" : !u ? "null schedule" : "nsteps must be >= 1" ); return -1; }
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  const size_t n = (size_t)b->batch*nsteps*b->nlink;
+  /* the staging may still feed the copies of the previous call (they wait for its steps on the streams that made them) */
+  for( int k=0; k<b->ctrl_nev; k++ ) HIPCHK( hipEventSynchronize( b->ctrl_ev[k] ), -1 );
+  if( n > b->ctrl_cap ){
+    /* the old device copy may still be read by launches of earlier calls */
+    if( sync_streams( b ) < 0 ) return -1;
+    HIPCHK( hipDeviceSynchronize(), -1 );
+    (void)hipFree( b->d_ctrl ); b->d_ctrl = NULL;
+    if( b->h_ctrl ){ (void)hipHostFree( b->h_ctrl ); b->h_ctrl = NULL; }
+    b->ctrl_cap = 0;
+    HIPCHK( hipMalloc( (void **)&b->d_ctrl, sizeof(double)*n ), -1 );
+    HIPCHK( hipHostMalloc( (void **)&b->h_ctrl, sizeof(double)*n, hipHostMallocDefault ), -1 );
+    b->ctrl_cap = n;
+  }
+  if( !b->ctrl_ev[0] )
+    for( int k=0; k<RKFD_MAX_SPLIT; k++ ) HIPCHK( hipEventCreateWithFlags( &b->ctrl_ev[k], hipEventDisableTiming ), -1 );
+  memcpy( b->h_ctrl, u, sizeof(double)*n );
+  return launch( b, 0, nsteps, stream, b->d_ctrl, true );
+}
+/* the same with a schedule the caller keeps on the batch's device ([batch][nsteps][nlink] doubles), read in stream order after
+ * `stream`: it must stay untouched until the steps are done (rkfdBatchJoin / rkfdBatchStatus) */
+extern "C" int rkfdBatchUpdateControlledDev(rkfdBatch *b, int nsteps, const double *u_dev, void *stream)
+{
+  if( !b || !u_dev || nsteps < 1 ){ SETERR( "rkfdBatchUpdateControlledDev: %s", !b ? "null batch" : !u_dev ? "null schedule" : "nsteps must be >= 1" ); return -1; }
+  return launch( b, 0, nsteps, stream, u_dev, false );
+}
 
 /* diagnostic: nsteps x rkFDUpdate with in-kernel phase stamps; out[batch][8] shader-clock cycles of
  * {kinematics, collision+penalty, sweep 2, sweep 3, MLCP, tail, unused, whole launch}.  Synchronous. */

@@ -48,7 +48,7 @@ static const rkfdRccl *rccl_api(void)
   return state == 1 ? &api : NULL;
 }
 
-enum { NODE_CMD_NONE = 0, NODE_CMD_INIT, NODE_CMD_UPDATE, NODE_CMD_SPECIALIZE, NODE_CMD_SPLIT, NODE_CMD_STEPS_PER_LAUNCH, NODE_CMD_TUNE, NODE_CMD_STATUS, NODE_CMD_SNAPSHOT, NODE_CMD_RESTORE, NODE_CMD_PACK, NODE_CMD_QUIT };
+enum { NODE_CMD_NONE = 0, NODE_CMD_INIT, NODE_CMD_UPDATE, NODE_CMD_SPECIALIZE, NODE_CMD_SPLIT, NODE_CMD_STEPS_PER_LAUNCH, NODE_CMD_TUNE, NODE_CMD_STATUS, NODE_CMD_SNAPSHOT, NODE_CMD_RESTORE, NODE_CMD_PACK, NODE_CMD_UPDATE_CTRL, NODE_CMD_QUIT };
 
 struct rkfdNode;
 struct rkfdNodeWorker {
@@ -69,6 +69,7 @@ struct rkfdNode {
   pthread_mutex_t mu;
   pthread_cond_t cv_cmd, cv_done;
   int cmd, arg, seq, done;
+  const double *ctrl;        /* NODE_CMD_UPDATE_CTRL: the caller's host schedule [total][arg][nlink] */
   /* gather */
   std::vector<ncclComm_t> comm;
   int have_comm;
@@ -81,6 +82,7 @@ static int node_run_on(rkfdNode *n, int k, int cmd, int arg)
   switch( cmd ){
   case NODE_CMD_INIT:       return rkfdBatchUpdateInit( b, n->st[k] );
   case NODE_CMD_UPDATE:     return rkfdBatchUpdate( b, arg, n->st[k] );
+  case NODE_CMD_UPDATE_CTRL: return rkfdBatchUpdateControlled( b, arg, n->ctrl + (size_t)n->lo[k]*arg*n->nlink, n->st[k] );
   case NODE_CMD_SPECIALIZE: return rkfdBatchSpecialize( b );
   case NODE_CMD_SPLIT:      return rkfdBatchSetSplit( b, arg );
   case NODE_CMD_STEPS_PER_LAUNCH: return rkfdBatchSetStepsPerLaunch( b, arg );
@@ -184,7 +186,7 @@ extern "C" rkfdNode *rkfdNodeCreate(const rkfdModel *m, int total, int max_rigid
   if( ndev > total ) ndev = total;
   rkfdNode *n = new rkfdNode();
   n->ndev = ndev; n->total = total; n->ndof = m->ndof; n->nlink = m->nlink; n->ncand = m->ncand; n->have_comm = 0;
-  n->cmd = NODE_CMD_NONE; n->arg = 0; n->seq = 0; n->done = 0;
+  n->cmd = NODE_CMD_NONE; n->arg = 0; n->seq = 0; n->done = 0; n->ctrl = NULL;
   pthread_mutex_init( &n->mu, NULL ); pthread_cond_init( &n->cv_cmd, NULL ); pthread_cond_init( &n->cv_done, NULL );
   n->dev.resize( ndev ); n->lo.resize( ndev ); n->hi.resize( ndev );
   n->b.assign( ndev, NULL ); n->st.assign( ndev, NULL ); n->d_send.assign( ndev, NULL ); n->d_recv.assign( ndev, NULL );
@@ -263,6 +265,14 @@ extern "C" int rkfdNodeUpdate(rkfdNode *n, int nsteps){ if( !n ){ SETERR( "null 
 extern "C" int rkfdNodeSnapshot(rkfdNode *n){ if( !n ){ SETERR( "null node" ); return -1; } return node_all( n, NODE_CMD_SNAPSHOT, 0 ); }
 extern "C" int rkfdNodeRestore(rkfdNode *n){ if( !n ){ SETERR( "null node" ); return -1; } return node_all( n, NODE_CMD_RESTORE, 0 ); }
 extern "C" int rkfdNodeStatus(rkfdNode *n){ if( !n ){ SETERR( "null node" ); return -1; } return node_all( n, NODE_CMD_STATUS, 0 ); }
+extern "C" int rkfdNodeUpdateControlled(rkfdNode *n, int nsteps, const double *u)
+{
+  if( !n || !u || nsteps < 1 ){ SETERR( "rkfdNodeUpdateControlled: %s", !n ? "null node" : !u ? "null schedule" : "nsteps must be >= 1" ); return -1; }
+  n->ctrl = u;      /* (read by the workers only while node_all waits for them: every copy out of u is made before it returns) */
+  const int r = node_all( n, NODE_CMD_UPDATE_CTRL, nsteps );
+  n->ctrl = NULL;
+  return r;
+}
 
 /* the path's only collective: every device contributes its block of final {dis, vel} ([mx][2 ndof] doubles, its own instances
  * first, padded to the largest shard) to one ncclAllGather; afterwards EVERY device holds the final states of all `total`
