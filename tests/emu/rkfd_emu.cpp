@@ -143,3 +143,15 @@ extern "C" int rkfd_emu_run(const rkfdModel *m, int max_rigid, rkfdDevState *st,
   rkfd_devmodel_free( &h );
   return errflag;
 }
+
+/* what the device-model builder picks for a world with 8 / ngroup instances per wavefront (the tests' path helper checks its
+ * rules against it, tests/solver_paths.py): out = { vert_rigid, ma_packed, ma_size, lds_bytes, lds_shared }; -1 when it refuses */
+extern "C" int rkfd_emu_layout(const rkfdModel *m, int max_rigid, int ngroup, int *out)
+{
+  rkfdDevModelHost h;
+  char err[256];
+  if( rkfd_devmodel_build_w( m, max_rigid, ngroup, &h, err, sizeof(err) ) < 0 ) return -1;
+  out[0] = h.dm.vert_rigid; out[1] = h.dm.ma_packed; out[2] = h.dm.ma_size; out[3] = (int)h.lds_bytes; out[4] = h.dm.lds_shared;
+  rkfd_devmodel_free( &h );
+  return 0;
+}
