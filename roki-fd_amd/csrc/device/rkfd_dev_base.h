@@ -16,7 +16,7 @@
    int    rkfd_emu_half(void);
 #  define HALF()        rkfd_emu_half()
 #  define SYNC()        rkfd_emu_sync()
-#  define SYNCW()       rkfd_emu_sync_wave()      /* all live instances of the wavefront (two instances per wavefront: the shared tables) */
+#  define SYNCW()       rkfd_emu_sync_wave()      /* all live instances of the wavefront */
    double rkfd_emu_g8bcast(double x, int k);
 #  define G8SUM(x)      rkfd_emu_g8sum(x)
 #  define G8SUM2(x,y)   do{ (x) = rkfd_emu_g8sum(x); (y) = rkfd_emu_g8sum(y); }while(0)
@@ -351,6 +351,16 @@ RKFD_DEV double d_clamp(double x, double lo, double hi){ return x < lo ? lo : ( 
 
 /* ------------------------------------------------------------------------ */
 /* LDS carve-up for one instance */
+/* Where the world's static tables (CIp, LI, CHP, CFO, PL) live.  Two instances per wavefront, worlds without breakable joints: in
+ * the device model in global memory (rkfdDevModel.tabs), and in the kernels compiled for such a world the pointers are typed
+ * global, so that every table read is a global_load (a generic pointer would give flat loads: the compiler loses the address
+ * space of a model pointer copied out of the kernel argument, and a flat load also counts against the lgkmcnt every SYNC() waits
+ * for).  Everywhere else: each instance's own copy in LDS, generic pointers as before. */
+#if !defined(RKFD_EMU) && defined(__HIP_DEVICE_COMPILE__) && defined(RKFD_SPEC) && RKFD_W == 2 && !RKFD_SPEC_HAS_BRF
+#  define RKFD_TAB __attribute__((address_space(1)))
+#else
+#  define RKFD_TAB
+#endif
 typedef struct {
   double *q, *qd;                 /* [ndof] each; live from the integrator's update to the first look of the next evaluation:
                                      ALIAS the head of PB|AC|C */
@@ -391,11 +401,11 @@ typedef struct {
   unsigned short *lrg, *lel;      /* [maxact] candidates in rigid / elastic contact, in candidate order */
   unsigned char *act, *typ;       /* [NC] in contact, stick / slip type                   */
   unsigned char *asl;             /* [NC] active-contact slot of a candidate              */
-  int *LI;                        /* [NL] packed link info (RKFD_LI_*)                    */
-  int *CIp;                       /* [NC] packed candidate info                           */
-  unsigned short *CFO;            /* [NC] first plane of the candidate's partner shape    */
-  unsigned short *CHP;            /* [NL] children lists (CSR values; offsets in the schedule): child | ( its pool slot + 1 ) << 8 */
-  unsigned char *PL;              /* [NL*nlevel] ancestor at depth d (MLCP only), one byte each */
+  RKFD_TAB int *LI;               /* [NL] packed link info (RKFD_LI_*)                    */
+  RKFD_TAB int *CIp;              /* [NC] packed candidate info                           */
+  RKFD_TAB unsigned short *CFO;   /* [NC] first plane of the candidate's partner shape    */
+  RKFD_TAB unsigned short *CHP;   /* [NL] children lists (CSR values; offsets in the schedule): child | ( its pool slot + 1 ) << 8 */
+  RKFD_TAB unsigned char *PL;     /* [NL*nlevel] ancestor at depth d (MLCP only), one byte each */
   unsigned char *BRK;             /* [NL] worlds with breakable float joints only: 0 no such joint, 1 unbroken, 2 broken (rkfd_dev_brf.h) */
   /* Volume plugin (kernel variant sv == 2 only; rkfd_dev_volume.h): per colliding pair VD [np*48] and its contact-plane
    * conditions VPL [np*ncp*8]; face polygons VPOLY [nf*pv*3] and reduction scratch VRED [16*nf+16] of the collision phase, sharing
@@ -410,8 +420,8 @@ typedef struct {
 } rkfdLds;
 RKFD_DEV void rkfd_lds_carve(rkfdLds *L, void *base, int NL, int ND, int NC, int M, int nlevel, int npool, int nfloat, int maxact, int nside, int pu_alias, int npurow, int vert_rigid, int has_slide, int ma_size,
                              int vol_np, int vol_ncp, int vol_pv, int vol_nf, int pyramid, int has_pl, void *shared = 0)
-/* must match the byte count computed in rkfd_devmodel.cpp.  shared != 0: the world's static tables live there (once per wavefront,
- * rkfdDevModel.lds_shared) instead of in the instance's own block */
+/* must match the byte count computed in rkfd_devmodel.cpp.  shared != 0: the world's static tables are read from there (global
+ * memory, rkfdDevModel.tabs: two instances per wavefront) instead of from the instance's own block */
 {
   double *d = (double *)base;
   L->S = d; d += NL*6;
@@ -464,21 +474,22 @@ RKFD_DEV void rkfd_lds_carve(rkfdLds *L, void *base, int NL, int ND, int NC, int
   }
   int *ip = (int *)d;
   int *sip = (int *)shared;
-  if( shared ){ L->CIp = sip; sip += NC; } else { L->CIp = ip; ip += NC; }
+  if( shared ){ L->CIp = (RKFD_TAB int *)sip; sip += NC; } else { L->CIp = (RKFD_TAB int *)ip; ip += NC; }
   L->tgt = ip; ip += nside*maxact; L->cnt = ip; ip += vol_np ? 12 : ( NC > 0 ? 8 : 4 );
   L->VI = ip; if( vol_np ) ip += 2*vol_np;
   L->GC = ip; if( RKFD_GC_NEEDED( M ) ) ip += RKFD_GC_INTS;
-  if( shared ){ L->LI = sip; sip += NL; } else { L->LI = ip; ip += NL; }
+  if( shared ){ L->LI = (RKFD_TAB int *)sip; sip += NL; } else { L->LI = (RKFD_TAB int *)ip; ip += NL; }
   unsigned short *sp = (unsigned short *)ip;
   unsigned short *ssp = (unsigned short *)sip;
-  if( shared ){ L->CHP = ssp; ssp += NL; L->CFO = ssp; ssp += NC; } else { L->CHP = sp; sp += NL; L->CFO = sp; sp += NC; }
+  if( shared ){ L->CHP = (RKFD_TAB unsigned short *)ssp; ssp += NL; L->CFO = (RKFD_TAB unsigned short *)ssp; ssp += NC; }
+  else { L->CHP = (RKFD_TAB unsigned short *)sp; sp += NL; L->CFO = (RKFD_TAB unsigned short *)sp; sp += NC; }
   L->lrg = sp; sp += maxact; L->lel = sp; sp += maxact;
   unsigned char *bp = (unsigned char *)sp;
   L->act = bp; bp += NC; L->typ = bp; bp += NC; L->asl = bp; bp += NC;
   L->FS = bp; bp += maxact;
   L->CRC = bp; if( vert_rigid ) bp += M;
   L->QA = bp; if( vert_rigid == 3 ) bp += ( pyramid+1 )*( M/3 );
-  if( shared ) L->PL = (unsigned char *)ssp; else { L->PL = bp; if( has_pl ) bp += NL*( nlevel+3 ); }
+  if( shared ) L->PL = (RKFD_TAB unsigned char *)ssp; else { L->PL = (RKFD_TAB unsigned char *)bp; if( has_pl ) bp += NL*( nlevel+3 ); }
   L->BRK = bp;
 }
 

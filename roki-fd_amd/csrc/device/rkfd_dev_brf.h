@@ -63,7 +63,7 @@ RKFD_DEV void rkfd_brf_after_kinematics(const rkfdDevModel &m, const rkfdLds &L)
   if( m.maxrg > 0 && lane < NL ){
     /* where a force on this link stops propagating upwards with the joint types of THIS evaluation: the nearest float joint at or
      * above it, else the root; 255 for a link that cannot move (fixed joints all the way up) */
-    unsigned char *TOP = L.PL + NL*m.nlevel;
+    RKFD_TAB unsigned char *TOP = L.PL + NL*m.nlevel;
     int a = lane;
     while( RKFD_LI_JT( L.LI[a] ) != RKFD_JOINT_FLOAT && RKFD_LI_PAR( L.LI[a] ) >= 0 ) a = RKFD_LI_PAR( L.LI[a] );
     bool stat = RKFD_LI_JT( L.LI[a] ) == RKFD_JOINT_FIXED;
@@ -91,7 +91,7 @@ RKFD_DEV void rkfd_brf_before_probes(const rkfdDevModel &m, const rkfdLds &L)
 RKFD_DEV void rkfd_brf_wrench_part(const rkfdDevModel &m, const rkfdLds &L)
 {
   const int lane = LANE();
-  const unsigned char *FSL = L.PL + m.nlink*m.nlevel + m.nlink;
+  RKFD_TAB const unsigned char *FSL = L.PL + m.nlink*m.nlevel + m.nlink;
   if( lane < m.nlink && L.BRK[lane] == RKFD_BRF_ATTACHED ){
     /* (the float-slot table lives with the path tables, which only worlds with a rigid contact capacity keep; otherwise count) */
     int fs = 0;
@@ -137,7 +137,7 @@ RKFD_DEV int rkfd_brf_fslot(const rkfdDevModel &m, const rkfdLds &L, int lane)
 RKFD_DEV void rkfd_brf_break_test(const rkfdDevModel &m, const rkfdLds &L, bool rigid)
 {
   const int lane = LANE();
-  const unsigned char *FSL = L.PL + m.nlink*m.nlevel + m.nlink;
+  RKFD_TAB const unsigned char *FSL = L.PL + m.nlink*m.nlevel + m.nlink;
   /* every joint is tested against the states of THIS evaluation (which joints are attached decides which contact forces a
    * joint carries): the verdicts are written only after every lane has read what it needs */
   bool breaks = false;

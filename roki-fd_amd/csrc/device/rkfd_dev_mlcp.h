@@ -584,8 +584,8 @@ template<bool prof, bool vqp, bool pk> RKFD_DEV void rkfd_phase_mlcp(const rkfdD
   const int NLV = m.nlevel, NL = m.nlink, NR = m.npurow;
   const int NSD = m.nside;
   const int PUS = 3*m.maxrg;                          /* columns between the two sides of PU (RKFD_PU_AT) */
-  const unsigned char *TOP = L.PL + NL*NLV;           /* where a force on a link stops propagating (255: static) */
-  const unsigned char *FSL = TOP + NL;                /* float slot of a link */
+  RKFD_TAB const unsigned char *TOP = L.PL + NL*NLV;           /* where a force on a link stops propagating (255: static) */
+  RKFD_TAB const unsigned char *FSL = TOP + NL;                /* float slot of a link */
   const double dt = m.dt;
 
   /* b: free relative acceleration, then *dt + relative velocity + compensation
@@ -683,7 +683,7 @@ template<bool prof, bool vqp, bool pk> RKFD_DEV void rkfd_phase_mlcp(const rkfdD
 #pragma unroll
         for( int k=0; k<6; k++ ) dp[k] = sg*W[k];
         double *pu = &L.PU[RKFD_PU_AT( m, s2, col, 0 )];
-        const unsigned char *path = &L.PL[a*NLV];
+        RKFD_TAB const unsigned char *path = &L.PL[a*NLV];
         double Sx[6], Ux[6], sdx, dix;
 #pragma unroll
         for( int k=0; k<6; k++ ){ Sx[k] = L.S[6*a+k]; Ux[k] = L.U[6*a+k]; }

@@ -138,7 +138,7 @@ RKFD_DEV void rkfd_cat_dis(const rkfdDevModel &m, const rkfdLds &L, int dofkind,
  * for the four Runge-Kutta-Gill stages and the committing evaluation of its step; the last step's input is stored to st.motor_in
  * (for the model links the device simulates - a link merged into its parent has no motor the device reads). */
 template<bool prof, int vqp, bool pk> RKFD_DEV void rkfd_instance(const rkfdDevModel &m_, const rkfdDevState &st, int b, void *ldsbase,
-                            int mode, int nsteps, int *errflag, bool live = true, void *ldsshared = 0,
+                            int mode, int nsteps, int *errflag, bool live = true, void * /* ignored: the LDS behind the instances' blocks (lds_shared, now 0); the lane emulator still passes it */ = 0,
                             const double *ctrl = nullptr, int ctrl_stride = 0)
 {
 #ifdef RKFD_SPEC
@@ -153,18 +153,22 @@ template<bool prof, int vqp, bool pk> RKFD_DEV void rkfd_instance(const rkfdDevM
   m.npurow = RKFD_SPEC_NPUROW; m.pu_d0 = RKFD_SPEC_PU_D0; m.pu_alias = RKFD_SPEC_PU_ALIAS; m.vert_rigid = RKFD_SPEC_VERT_RIGID; m.qscr_alias = RKFD_SPEC_QSCR_ALIAS;
   m.has_slide = RKFD_SPEC_HAS_SLIDE; m.ma_size = RKFD_SPEC_MA_SIZE; m.ma_packed = RKFD_SPEC_MA_PACKED;
   m.max_iter = RKFD_SPEC_MAX_ITER; m.solver = RKFD_SPEC_SOLVER; m.pyramid = RKFD_SPEC_PYRAMID; m.anchor = RKFD_SPEC_ANCHOR;
-  m.mlcp_mfma = RKFD_SPEC_MLCP_MFMA; m.has_brf = RKFD_SPEC_HAS_BRF; m.lds_shared = RKFD_SPEC_LDS_SHARED;
+  m.mlcp_mfma = RKFD_SPEC_MLCP_MFMA; m.has_brf = RKFD_SPEC_HAS_BRF;
   m.vol_npair = RKFD_SPEC_VOL_NPAIR; m.vol_np = RKFD_SPEC_VOL_NP; m.vol_ncp = RKFD_SPEC_VOL_NCP; m.vol_pv = RKFD_SPEC_VOL_PV; m.vol_nf = RKFD_SPEC_VOL_NF;
 #else
   const rkfdDevModel &m = m_;
 #endif
   const int lane = LANE();
   const int ND = m.ndof, NL = m.nlink, NC = m.ncand;
+  /* two instances per wavefront (worlds without breakable joints): the world's static tables are read from the device model in global
+   * memory (rkfdDevModel.tabs), which gives the LDS of a workgroup its sixth slot per CU on the humanoid; everywhere else every
+   * instance copies them into its own block.  Which of the two is fixed at compile time (RKFD_W; has_brf is a literal in the kernels
+   * compiled for one world); rkfd_dev_base.h: RKFD_TAB types the table pointers global where they point there */
+  const bool gtab = RKFD_W == 2 && !m.has_brf;
+  const bool fills = !gtab;
   rkfdLds L;
   rkfd_lds_carve( &L, ldsbase, NL, ND, NC, 3*m.maxrg, m.nlevel, m.npool, m.nfloat, m.maxact, m.nside, m.pu_alias, m.npurow, m.vert_rigid, m.has_slide, m.ma_size,
-                  vqp == 2 ? m.vol_np : 0, m.vol_ncp, m.vol_pv, m.vol_nf, m.pyramid, m.maxrg > 0, m.lds_shared > 0 ? ldsshared : 0 );
-  /* the world's static tables, once per wavefront where the instances share them: the first instance of the wavefront fills them */
-  const bool fills = !( m.lds_shared > 0 ) || HALF() == 0;
+                  vqp == 2 ? m.vol_np : 0, m.vol_ncp, m.vol_pv, m.vol_nf, m.pyramid, m.maxrg > 0, gtab ? (void *)m.tabs : 0 );
   if( m.lds_poison > 0 ){      /* (RKFD_DEBUG_POISON_LDS: see rkfd_devmodel.h) */
     for( int i=lane; i<m.lds_poison; i+=RKFD_WL ) ( (unsigned *)ldsbase )[i] = 0xffffffffu;
     SYNC();
@@ -227,7 +231,6 @@ template<bool prof, int vqp, bool pk> RKFD_DEV void rkfd_instance(const rkfdDevM
     }
   }
   SYNC();
-  if( m.lds_shared > 0 ) SYNCW();
   int err = 0;
   /* phase-cycle counters exist only in the diagnostic instantiation (prof = true) */
   unsigned long long pc[prof ? RKFD_NPROF : 1];

@@ -1016,7 +1016,7 @@ template<bool prof> RKFD_DEV void rkfd_phase_volume(const rkfdDevModel &m, const
   const int np = L.cnt[CNT_NVP], n = 6*np, ld = n+1;
   const int NCP = m.vol_ncp;
   const int NLV = m.nlevel, NL = m.nlink, NR = m.npurow, NSD = m.nside;
-  const unsigned char *TOP = L.PL + NL*NLV, *FSL = TOP + NL, *FLK = FSL + NL;
+  RKFD_TAB const unsigned char *TOP = L.PL + NL*NLV, *FSL = TOP + NL, *FLK = FSL + NL;
   const double dt = m.dt;
 
   /* b = dt x free 6-D relative acceleration at the centre + relative velocity (:143-154, :214-226); the moving sides */
@@ -1076,7 +1076,7 @@ template<bool prof> RKFD_DEV void rkfd_phase_volume(const rkfdDevModel &m, const
 #pragma unroll
       for( int k=0; k<6; k++ ) dp[k] = sg*W[k];
       double *pu = &L.PU[RKFD_PU_AT( m, s2, col, 0 )];
-      const unsigned char *path = &L.PL[a*NLV];
+      RKFD_TAB const unsigned char *path = &L.PL[a*NLV];
       for( int d=da; d>=d0; d-- ){
         const int il = path[d];
         double du = 0;

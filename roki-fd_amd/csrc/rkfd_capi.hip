@@ -106,6 +106,7 @@ struct rkfdBatch {
   int has_snap;
   int *d_err;
   size_t lds_bytes;
+  size_t lds_pad;         /* RKFD_LDS_PAD_BYTES (diagnostic): extra LDS every workgroup asks for, one instance per wavefront or two */
   rkfdKernel kern, kern_prof;
   /* rkfdBatchSpecialize: the step kernel compiled for this world (hipRTC); NULL = the generic kernels above */
   hipModule_t spec_mod;
@@ -178,7 +179,8 @@ extern "C" rkfdBatch *rkfdBatchCreate(const rkfdModel *m, int batch, int device,
   b->device = device; b->batch = batch; b->nlink = m->nlink; b->ndof = m->ndof; b->ncand = m->ncand;
   b->lds_bytes = b->host.lds_bytes;
   /* diagnostic (tools/sweep_residency.sh): ask for more LDS than needed, to measure throughput against residency */
-  if( const char *pad = getenv( "RKFD_LDS_PAD_BYTES" ) ) b->lds_bytes += (size_t)( atoi( pad ) > 0 ? atoi( pad ) : 0 );
+  if( const char *pad = getenv( "RKFD_LDS_PAD_BYTES" ) ) b->lds_pad = (size_t)( atoi( pad ) > 0 ? atoi( pad ) : 0 );
+  b->lds_bytes += b->lds_pad;
   if( b->lds_bytes > 160*1024 ){
     SETERR( "rkfdBatchCreate: one instance needs %zu bytes of LDS (> 160 KiB)", b->lds_bytes );
     rkfdBatchDestroy( b );
@@ -251,6 +253,9 @@ extern "C" int rkfdLdsBytesFor(const rkfdModel *m, int max_rigid)
   return n;
 }
 
+/* what a workgroup of the kernel with two instances per wavefront asks for: two instance blocks (and the diagnostic pad) */
+static size_t wg2_bytes(const rkfdBatch *b){ return 2*b->host2.lds_bytes + b->lds_pad; }
+
 extern "C" int rkfdBatchSize(const rkfdBatch *b){ return b ? b->batch : -1; }
 extern "C" int rkfdBatchDof(const rkfdBatch *b){ return b ? b->ndof : -1; }
 extern "C" int rkfdBatchLdsBytes(const rkfdBatch *b){ return b ? (int)b->lds_bytes : -1; }
@@ -265,7 +270,7 @@ extern "C" int rkfdBatchResidency(const rkfdBatch *b)
   if( pieces > 0 && 128/pieces < n ) n = 128/pieces;
   if( b->ipw == 2 && b->spec_fn ){
     /* two instances per wavefront: workgroups of 2 x the LDS, at most two waves per SIMD (the kernel is built for that) */
-    const int p2 = (int)( ( 2*b->host2.lds_bytes + (size_t)b->host2.dm.lds_shared + 1279 )/1280 );
+    const int p2 = (int)( ( wg2_bytes( b ) + 1279 )/1280 );
     int w = p2 > 0 ? 128/p2 : 0;
     if( w > 8 ) w = 8;
     n = 2*w;
@@ -425,7 +430,7 @@ static int launch_one(rkfdBatch *b, rkfdKernel kern, int count, int first, int m
       rkfdDevState st2 = b->st;
       st2.batch = first + count;
       void *args[] = { &b->dm2, &st2, &first, &mode, &nsteps, &b->d_err, &ctrl, &ctrl_stride };
-      HIPCHK( hipModuleLaunchKernel( b->spec_fn, ( count+1 )/2, 1, 1, RKFD_WAVE, 1, 1, (unsigned)( 2*b->host2.lds_bytes + (size_t)b->host2.dm.lds_shared ), stream, args, NULL ), -1 );
+      HIPCHK( hipModuleLaunchKernel( b->spec_fn, ( count+1 )/2, 1, 1, RKFD_WAVE, 1, 1, (unsigned)wg2_bytes( b ), stream, args, NULL ), -1 );
       return 0;
     }
     void *args[] = { &b->dm, &b->st, &first, &mode, &nsteps, &b->d_err, &ctrl, &ctrl_stride };
@@ -508,7 +513,7 @@ static std::string spec_source(const rkfdDevModel &d, int ipw = 1)
     "#define RKFD_SPEC_NPUROW %d\n#define RKFD_SPEC_PU_D0 %d\n#define RKFD_SPEC_PU_ALIAS %d\n#define RKFD_SPEC_VERT_RIGID %d\n#define RKFD_SPEC_QSCR_ALIAS %d\n"
     "#define RKFD_SPEC_HAS_SLIDE %d\n#define RKFD_SPEC_MA_SIZE %d\n#define RKFD_SPEC_MA_PACKED %d\n"
     "#define RKFD_SPEC_MAX_ITER %d\n#define RKFD_SPEC_SOLVER %d\n#define RKFD_SPEC_PYRAMID %d\n#define RKFD_SPEC_ANCHOR %d\n#define RKFD_SPEC_MLCP_MFMA %d\n"
-    "#define RKFD_SPEC_HAS_BRF %d\n#define RKFD_SPEC_LDS_INSTANCE %d\n#define RKFD_SPEC_LDS_SHARED %d\n"
+    "#define RKFD_SPEC_HAS_BRF %d\n#define RKFD_SPEC_LDS_INSTANCE %d\n"
     "#define RKFD_SPEC_VOL_NPAIR %d\n#define RKFD_SPEC_VOL_NP %d\n#define RKFD_SPEC_VOL_NCP %d\n#define RKFD_SPEC_VOL_PV %d\n#define RKFD_SPEC_VOL_NF %d\n"
     "#include \"rkfd_device.h\"\n"
     "extern \"C\" __global__ void __launch_bounds__(64, %d)\n"
@@ -519,11 +524,11 @@ static std::string spec_source(const rkfdDevModel &d, int ipw = 1)
     "  if( RKFD_W == 1 && b >= st.batch ) return;\n"
     "  const bool live = b < st.batch;\n"
     "  if( !live ) b -= 1;\n"
-    "  rkfd_instance<false, %s, %s>( m, st, b, lds + HALF()*RKFD_SPEC_LDS_INSTANCE, mode, nsteps, errflag, live, lds + RKFD_W*RKFD_SPEC_LDS_INSTANCE, ctrl, ctrl_stride );\n"
+    "  rkfd_instance<false, %s, %s>( m, st, b, lds + HALF()*RKFD_SPEC_LDS_INSTANCE, mode, nsteps, errflag, live, nullptr, ctrl, ctrl_stride );\n"
     "}\n",
     ipw, d.nlink, d.ndof, d.ncand, d.nlink_model, d.nlevel, d.nround, d.nsched, d.maxrg, d.npool, d.nfloat, d.maxact, d.nside,
     d.npurow, d.pu_d0, d.pu_alias, d.vert_rigid, d.qscr_alias, d.has_slide, d.ma_size, d.ma_packed, d.max_iter, d.solver, d.pyramid, d.anchor, d.mlcp_mfma,
-    d.has_brf, d.lds_instance, ipw == 2 ? d.lds_shared : 0, d.vol_npair, d.vol_np, d.vol_ncp, d.vol_pv, d.vol_nf,
+    d.has_brf, d.lds_instance, d.vol_npair, d.vol_np, d.vol_ncp, d.vol_pv, d.vol_nf,
     ( d.vol_np > 0 || ipw == 2 || d.vert_rigid == 2 ) ? 2 : 3, d.vol_np > 0 ? "2" : ( d.vert_rigid ? "1" : "0" ), d.ma_packed ? "true" : "false" );
   std::string src;
   if( const char *pre = getenv( "RKFD_SPEC_DEFINE" ) ){      /* diagnostic: NAME[,NAME...] defined as 1 in front of the source */
@@ -738,6 +743,15 @@ extern "C" int rkfdBatchSpecialize(rkfdBatch *b)
   HIPCHK( hipModuleLoadData( &b->spec_mod, code.data() ), -1 );
 
   HIPCHK( hipModuleGetFunction( &b->spec_fn, b->spec_mod, "rkfd_step_kernel_spec" ), -1 );
+  if( b->ipw == 2 && wg2_bytes( b ) > 64*1024 ){
+    /* (a workgroup of two instances above 64 KiB of LDS needs the opt-in, as the generic kernels get it in rkfdBatchCreate) */
+    const hipError_t e = hipFuncSetAttribute( (const void *)b->spec_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg2_bytes( b ) );
+    if( e != hipSuccess ){
+      (void)hipModuleUnload( b->spec_mod ); b->spec_mod = NULL; b->spec_fn = NULL;
+      SETERR( "hipFuncSetAttribute(LDS=%zu) failed: %s", wg2_bytes( b ), hipGetErrorString( e ) );
+      return -1;
+    }
+  }
   {
     /* the compiler behind hipRTC is whichever libamd_comgr the process loaded first; a framework that bundles an older
      * one (PyTorch does) gives a kernel that spills (437 VGPR spills, 3.9 M instead of 14 M steps/s on config 4): refuse it */
@@ -768,7 +782,7 @@ extern "C" int rkfdBatchSetInstancesPerWave(rkfdBatch *b, int ipw)
   if( !b->dblob2 ){
     char err[256];
     if( rkfd_devmodel_build_w( b->model_for_w2, b->host.dm.maxrg, 4, &b->host2, err, sizeof(err) ) < 0 ){ SETERR( "rkfdBatchSetInstancesPerWave: %s", err ); return -1; }
-    if( b->host2.lds_bytes*2 + (size_t)b->host2.dm.lds_shared > 160*1024 ){ SETERR( "rkfdBatchSetInstancesPerWave: two instances need %zu bytes of LDS (> 160 KiB)", 2*b->host2.lds_bytes ); rkfd_devmodel_free( &b->host2 ); return -1; }
+    if( wg2_bytes( b ) > 160*1024 ){ SETERR( "rkfdBatchSetInstancesPerWave: two instances need %zu bytes of LDS (> 160 KiB)", wg2_bytes( b ) ); rkfd_devmodel_free( &b->host2 ); return -1; }
     HIPCHK( hipMalloc( &b->dblob2, b->host2.bytes ), -1 );
     HIPCHK( hipMemcpy( b->dblob2, b->host2.blob, b->host2.bytes, hipMemcpyHostToDevice ), -1 );
     b->dm2 = b->host2.dm;
@@ -832,12 +846,14 @@ extern "C" int rkfdBatchTuneInstancesPerWave(rkfdBatch *b, int nsteps, double *m
     b->spec_mod = NULL; b->spec_fn = NULL;
     int two = rkfdBatchSetInstancesPerWave( b, 2 );
     if( two == 0 ) two = rkfdBatchSpecialize( b );
-    if( two == 0 ) r = tune_time( b, nsteps, &t[1] );
-    if( two == 0 && r == 0 && t[1] < t[0] ){ (void)hipModuleUnload( mod1 ); chosen = 2; }
+    /* a failed measurement of two (a launch the device refuses, say) makes the world not eligible, as a failed build does:
+     * one instance per wavefront stays, and t[1] < 0 says so; the state goes back from the snapshot below either way */
+    if( two == 0 && tune_time( b, nsteps, &t[1] ) < 0 ){ two = -1; t[1] = -1; (void)hipGetLastError(); }
+    if( two == 0 && t[1] < t[0] ){ (void)hipModuleUnload( mod1 ); chosen = 2; }
     else{
       if( b->spec_mod ) (void)hipModuleUnload( b->spec_mod );
       b->spec_mod = mod1; b->spec_fn = fn1; b->ipw = 1;
-      if( r == 0 ) chosen = 1;
+      chosen = 1;
     }
   }
   /* the state as it was, and the caller's snapshot back in place */

@@ -656,6 +656,22 @@ extern "C" int rkfd_devmodel_build_w(const rkfdModel *m, int max_rigid, const in
     if( R_jtype[i] == RKFD_DJT_SPHX ){ dofkind[R_dofoff[i]] = 1; dofkind[R_dofoff[i]+1] = 2; dofkind[R_dofoff[i]+2] = 2; }   /* angle-axis coordinates */
   }
   if( nround > RKFD_MAX_ROUND ) FAIL( "tree too deep" );
+  /* two instances per wavefront, worlds without breakable joints: the static tables the phases read - CIp, LI (ints), CHP, CFO
+   * (16 bit), PL (bytes) - in the packed form and order of rkfd_lds_carve's table block, read from here (global memory) instead
+   * of from a copy in LDS; with breakable joints the link info and the path tops are per instance and stay in LDS */
+  const bool gtab = NG == 4 && !has_brf;
+  const size_t tab_ints = (size_t)NC + (size_t)NL, tab_bytes = (size_t)2*NL + (size_t)2*NC + ( max_rigid > 0 ? (size_t)NL*( nlevel+3 ) : 0 );
+  std::vector<unsigned char> tabs( gtab ? tab_ints*sizeof(int) + tab_bytes : 0 );
+  if( gtab ){
+    int *ti = (int *)tabs.data();
+    for( int j=0; j<NC; j++ ) *ti++ = cinfo[j];
+    for( int i=0; i<NL; i++ ) *ti++ = linfo[i];
+    unsigned short *ts = (unsigned short *)ti;
+    for( int i=0; i<NL; i++ ){ const int ch = child_idx[i]; *ts++ = (unsigned short)( ch | ( ( pslot[ch]+1 ) << 8 ) ); }
+    for( int j=0; j<NC; j++ ) *ts++ = (unsigned short)cfo[j];
+    unsigned char *tb = (unsigned char *)ts;
+    if( max_rigid > 0 ) for( size_t k=0; k<(size_t)NL*( nlevel+3 ); k++ ) *tb++ = (unsigned char)pathlink[k];
+  }
   /* record offsets first (the vector may reallocate), then resolve */
   struct Ent { const void **slot; size_t off; };
   std::vector<Ent> ents;
@@ -680,6 +696,7 @@ extern "C" int rkfd_devmodel_build_w(const rkfdModel *m, int max_rigid, const in
   PUT( linfo, linfo.data(), sizeof(int)*NL ); PUT( cinfo, cinfo.data(), sizeof(int)*NC );
   PUT( sched, sched.data(), sizeof(int)*sched.size() );
   PUT( pslot, pslot.data(), sizeof(int)*NL );
+  PUT( tabs, tabs.data(), tabs.size() );
   PUT( cand_linkA, cA.data(), sizeof(int)*NC ); PUT( cand_linkB, cB.data(), sizeof(int)*NC );
   PUT( cand_foff, cfo.data(), sizeof(int)*NC ); PUT( cand_nf, cnf.data(), sizeof(int)*NC );
   PUT( cand_ci, cci.data(), sizeof(int)*NC ); PUT( cand_vert, cv.data(), sizeof(double)*3*NC ); PUT( cand_bs, cbs.data(), sizeof(double)*4*( NC ? NC : 1 ) );
@@ -736,22 +753,18 @@ extern "C" int rkfd_devmodel_build_w(const rkfdModel *m, int max_rigid, const in
                      + ( dm.vert_rigid ? ( dm.vert_rigid == 2 ? 0 : M*M ) + M*( M+1 )/2 + 5*M + 3*M : 0 )   /* Vert QP: QL, QW, QV, CR */
                      + ( dm.vert_rigid == 3 ? (size_t)dm.pyramid*M + (size_t)dm.pyramid*max_rigid : 0 )             /* ... wide form: QG, QY */
                      + ( vol_np > 0 ? (size_t)RKFD_VOL_LDS_DOUBLES( vol_np, vol_ncp, vol_pv, vol_nf, dm.pyramid ) : 0 );
-    /* two instances per wavefront: the world's static tables - CIp, LI (ints), CHP, CFO (16 bit), PL (bytes) - once per wavefront
-     * (rkfdDevModel.lds_shared); not with breakable joints, whose link info and path tops are per instance */
-    const bool shr = NG == 4 && !has_brf;
-    const size_t sh_ints = (size_t)NC + (size_t)NL, sh_bytes = (size_t)2*NL + (size_t)2*NC + ( max_rigid > 0 ? (size_t)NL*( nlevel+3 ) : 0 );
-    dm.lds_shared = shr ? (int)( ( sh_ints*sizeof(int) + sh_bytes + 15 ) & ~(size_t)15 ) : 0;
+    /* (gtab: the world's static tables are read from the device model, rkfdDevModel.tabs: not in the instance's block) */
     const size_t ints = (size_t)NC + (size_t)nside*maxact + ( vol_np > 0 ? 12 + 2*vol_np : ( NC > 0 ? 8 : 4 ) ) + (size_t)NL     /* CIp, tgt, cnt (VI), LI */
                       + ( RKFD_GC_NEEDED( (int)M ) ? RKFD_GC_INTS : 0 )                                                             /* GC */
-                      - ( shr ? sh_ints : 0 );
-    const size_t bytes = (size_t)2*NL + (size_t)5*NC + (size_t)5*maxact - ( shr ? sh_bytes : 0 ) + ( dm.vert_rigid ? M : 0 ) + ( dm.vert_rigid == 3 ? (size_t)( dm.pyramid+1 )*max_rigid : 0 )                                     /* CHP (16 bit), act typ asl (bytes) */
+                      - ( gtab ? tab_ints : 0 );
+    const size_t bytes = (size_t)2*NL + (size_t)5*NC + (size_t)5*maxact - ( gtab ? tab_bytes : 0 ) + ( dm.vert_rigid ? M : 0 ) + ( dm.vert_rigid == 3 ? (size_t)( dm.pyramid+1 )*max_rigid : 0 )                                     /* CHP (16 bit), act typ asl (bytes) */
                        + ( max_rigid > 0 ? (size_t)NL*( nlevel+3 ) : 0 )                 /* PL */
                        + ( has_brf ? (size_t)NL : 0 );                                   /* BRK */
     out->lds_bytes = dbl*sizeof(double) + ints*sizeof(int) + bytes;
     out->lds_bytes = ( out->lds_bytes + 15 ) & ~(size_t)15;
-    /* (what a workgroup asks for: one instance, or two and the shared tables) */
-    const size_t wg = NG == 4 ? 2*out->lds_bytes + (size_t)dm.lds_shared : out->lds_bytes;
-    const size_t wg_full = NG == 4 ? 2*lds_full + (size_t)dm.lds_shared : lds_full;
+    /* (what a workgroup asks for: one instance, or two) */
+    const size_t wg = NG == 4 ? 2*out->lds_bytes : out->lds_bytes;
+    const size_t wg_full = NG == 4 ? 2*lds_full : lds_full;
     if( pass == 0 ) lds_full = out->lds_bytes;
     else if( 128/( ( wg+1279 )/1280 ) <= 128/( ( wg_full+1279 )/1280 ) ){
       /* no instance gained: stay with full rows */
@@ -762,7 +775,7 @@ extern "C" int rkfd_devmodel_build_w(const rkfdModel *m, int max_rigid, const in
                NL, ND, NC, nlevel, npool, nfloat, maxact, nside, npurow, dm.pu_alias, (int)M, stage, (size_t)14*NL + pool, dm.vert_rigid, out->lds_bytes );
   }
   out->dm.ma_packed = dm.ma_packed; out->dm.ma_size = dm.ma_size;
-  out->dm.lds_instance = (int)out->lds_bytes; out->dm.lds_shared = dm.lds_shared;
+  out->dm.lds_instance = (int)out->lds_bytes; out->dm.lds_shared = 0;
   if( NG == 4 ){
     /* two instances per wavefront: everything that is one lane per item must fit the 32 lanes of an instance */
     if( NL > 32 || ND > 32 || dm.maxact > 32 || max_rigid > 16 || dm.vert_rigid || vol_np > 0 )
@@ -785,7 +798,7 @@ extern "C" void rkfd_devmodel_rebase(rkfdDevModel *dm, const void *from, const v
   RB(parent); RB(jtype); RB(dofoff); RB(mtype); RB(depth); RB(is_static);
   RB(org); RB(mass); RB(com); RB(inertia); RB(stiff); RB(visc); RB(coulomb); RB(sfric);
   RB(mot_k); RB(mot_admit); RB(mot_vmax); RB(mot_vmin); RB(mot_gear); RB(mot_inertia);
-  RB(anc); RB(level_off); RB(level_link); RB(child_off); RB(child_idx); RB(pathlink); RB(linfo); RB(sched); RB(cinfo); RB(pslot); RB(orig); RB(dofkind); RB(brf); RB(brk_f); RB(brk_t);
+  RB(anc); RB(level_off); RB(level_link); RB(child_off); RB(child_idx); RB(pathlink); RB(linfo); RB(sched); RB(tabs); RB(cinfo); RB(pslot); RB(orig); RB(dofkind); RB(brf); RB(brk_f); RB(brk_t);
   RB(cand_linkA); RB(cand_linkB); RB(cand_foff); RB(cand_nf); RB(cand_ci); RB(cand_vert); RB(cand_bs); RB(cs_mode); RB(cs_par); RB(planes);
   RB(vol_pair); RB(vol_loop); RB(vol_lplane); RB(vol_lvert); RB(vol_slide);
   RB(ci_type); RB(ci_sf); RB(ci_kf); RB(ci_k); RB(ci_l); RB(ci_e); RB(ci_v);

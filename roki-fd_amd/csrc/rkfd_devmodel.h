@@ -89,10 +89,11 @@ typedef struct {
   const int *sched;
   int ngroup;            /* lane groups (links) per sweep iteration the schedule was built for: 8, or 4 for two instances per wavefront */
   int lds_instance;      /* bytes of LDS one instance owns (the second instance of a wavefront starts that far in) */
-  int lds_shared;        /* two instances per wavefront: bytes of the world's static tables (candidate info, link info, child / pool
-                            table, face offsets, path table) kept ONCE per wavefront behind the two instances' blocks; 0: every
-                            instance keeps its own (one instance per wavefront; worlds with breakable joints, whose link info and
-                            path tops are per instance) */
+  int lds_shared;        /* LDS a workgroup holds besides its instances' blocks: always 0 (the tables two instances of a wavefront once
+                            shared there are read from `tabs`); still reported by the lane emulator's layout query (rkfd_emu_layout) */
+  const unsigned char *tabs;   /* two instances per wavefront, worlds without breakable joints: the world's static tables (candidate info,
+                            link info, child / pool table, face offsets, path table) in the packed form of rkfd_lds_carve's table block -
+                            read from global memory, not copied to LDS; empty otherwise (every instance keeps its own copy in LDS) */
   int npool;             /* links whose articulated inertia must be staged in LDS for a gathering parent */
   int nfloat;            /* float joints (each owns a 6x6 Cholesky slot and a saved frame)          */
   const int *pslot;      /* [nlink] pool slot of the link, -1 when its Ia is handed over in registers */

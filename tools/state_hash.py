@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Bit-identity aid for kernel work: steps a seeded batch of each named workload on the GPU and prints a SHA-256 over the
 final states, accelerations, contact sets, anchors and forces.  Run before and after a change that must not move a bit.
-usage: python tools/state_hash.py [--batch 1024] [--steps 40] [--no-specialize] workload ..."""
+usage: python tools/state_hash.py [--batch 1024] [--steps 40] [--no-specialize] [--ipw 1|2] workload ..."""
 import argparse, hashlib, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -12,6 +12,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=1024)
 ap.add_argument("--steps", type=int, default=40)
 ap.add_argument("--no-specialize", action="store_true")
+ap.add_argument("--ipw", type=int, default=1, choices=(1, 2), help="instances per wavefront of the world-specific kernel")
 ap.add_argument("workloads", nargs="+")
 a = ap.parse_args()
 def vertbox(batch, pyramid=8):
@@ -37,6 +38,8 @@ for nm in a.workloads:
     sc = vertbox(a.batch) if nm == "vertbox" else vertbox(a.batch, 4) if nm == "vertbox4" else R.scenarios.CONFIGS[nm](batch=a.batch)
     b = R.Batch(sc["world"], a.batch, max_rigid=sc["max_rigid"])
     if not a.no_specialize and b.lds_bytes <= 64 * 1024:
+        if a.ipw == 2:
+            b.set_instances_per_wave(2)
         b.specialize()
     b.set_state(sc["dis"], sc["vel"]); b.update_init(); b.update(a.steps)
     st = b.status()
