@@ -39,7 +39,12 @@ $(BUILD)/rkfd_capi.o: $(CSRC)/rkfd_capi.hip $(CSRC)/rkfd_capi_node.inc $(BUILD)/
 	@grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|VGPRs Spill|SGPRs Spill" $(BUILD)/rkfd_capi.remarks | sed 's/.*remark: *//; s/ \[-Rpass.*//' > $(PKG)/kernel_resources.txt
 	@grep -vE "remark:|^ +[0-9]+ \||^ +\||\^" $(BUILD)/rkfd_capi.remarks || true
 
-$(LIB): $(HOST_OBJS) $(BUILD)/rkfd_capi.o
+# the same step kernels built for batches that carry per-instance physical parameters (RKFD_PARAMS = 1): their own report
+$(BUILD)/rkfd_capi_par.o: $(CSRC)/rkfd_capi_par.hip $(CSRC)/*.h $(CSRC)/device/*.h include/*.h | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(BUILD)/rkfd_capi_par.remarks || ( cat $(BUILD)/rkfd_capi_par.remarks; exit 1 )
+	@grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|VGPRs Spill|SGPRs Spill" $(BUILD)/rkfd_capi_par.remarks | sed 's/.*remark: *//; s/ \[-Rpass.*//' > $(PKG)/kernel_resources_par.txt
+
+$(LIB): $(HOST_OBJS) $(BUILD)/rkfd_capi.o $(BUILD)/rkfd_capi_par.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl -lpthread
 
 oracle:
@@ -50,7 +55,8 @@ oracle:
 spec: $(LIB)
 	python3 tools/make_spec.py
 
-emu: tests/emu/librkfd_emu.so tests/emu/librkfd_emu_w2.so tests/emu/librkfd_emu_ctrl.so tests/emu/librkfd_emu_ctrl_w2.so
+emu: tests/emu/librkfd_emu.so tests/emu/librkfd_emu_w2.so tests/emu/librkfd_emu_ctrl.so tests/emu/librkfd_emu_ctrl_w2.so \
+     tests/emu/librkfd_emu_par.so tests/emu/librkfd_emu_par_w2.so
 
 tests/emu/librkfd_emu.so: tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_device.h $(CSRC)/rkfd_devmodel.cpp $(CSRC)/*.h $(CSRC)/device/*.h include/*.h
 	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread $(INC) -o $@ tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_devmodel.cpp
@@ -66,8 +72,15 @@ tests/emu/librkfd_emu_ctrl.so: tests/emu/rkfd_emu_ctrl.cpp tests/emu/rkfd_emu.cp
 tests/emu/librkfd_emu_ctrl_w2.so: tests/emu/rkfd_emu_ctrl.cpp tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_device.h $(CSRC)/rkfd_devmodel.cpp $(CSRC)/*.h $(CSRC)/device/*.h include/*.h
 	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread -DRKFD_W=2 $(INC) -o $@ tests/emu/rkfd_emu_ctrl.cpp $(CSRC)/rkfd_devmodel.cpp
 
+# the harness with a table of per-instance physical parameters (rkfdBatchSetParam's launches), one and two instances per wavefront
+tests/emu/librkfd_emu_par.so: tests/emu/rkfd_emu_par.cpp tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_device.h $(CSRC)/rkfd_devmodel.cpp $(CSRC)/*.h $(CSRC)/device/*.h include/*.h
+	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread -DRKFD_PARAMS=1 $(INC) -o $@ tests/emu/rkfd_emu_par.cpp $(CSRC)/rkfd_devmodel.cpp
+
+tests/emu/librkfd_emu_par_w2.so: tests/emu/rkfd_emu_par.cpp tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_device.h $(CSRC)/rkfd_devmodel.cpp $(CSRC)/*.h $(CSRC)/device/*.h include/*.h
+	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread -DRKFD_W=2 -DRKFD_PARAMS=1 $(INC) -o $@ tests/emu/rkfd_emu_par.cpp $(CSRC)/rkfd_devmodel.cpp
+
 clean:
-	rm -rf $(BUILD) $(LIB) $(PKG)/spec tests/emu/librkfd_emu.so tests/emu/librkfd_emu_w2.so tests/emu/librkfd_emu_ctrl.so tests/emu/librkfd_emu_ctrl_w2.so
+	rm -rf $(BUILD) $(LIB) $(PKG)/spec tests/emu/librkfd_emu.so tests/emu/librkfd_emu_w2.so tests/emu/librkfd_emu_ctrl.so tests/emu/librkfd_emu_ctrl_w2.so tests/emu/librkfd_emu_par.so tests/emu/librkfd_emu_par_w2.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle emu spec clean

@@ -108,6 +108,8 @@ int rkfdBatchSetStepsPerLaunch(rkfdBatch *b, int steps);
 int rkfdBatchSpecialize(rkfdBatch *b);
 int rkfdSpecializeCompile(const rkfdModel *m, int max_rigid);
 int rkfdSpecializeCompileW(const rkfdModel *m, int max_rigid, int ipw);      /* ipw: instances per wavefront, 1 or 2 (below) */
+/* par = 1: the kernel for batches that carry a table of per-instance parameters (rkfdBatchSetParam below); `make spec` makes both */
+int rkfdSpecializeCompileP(const rkfdModel *m, int max_rigid, int ipw, int par);
 /* Ahead-of-time kernels: a specialised kernel is a function of the world's dimensions and the device sources only, so its code
  * object is kept in a directory beside the library (`spec/`; RKFD_SPEC_DIR overrides, RKFD_SPEC_STORE=0 switches the store off),
  * keyed by a hash of everything that goes into it.  `make spec` fills it for the worlds of BASELINE.json's configurations at
@@ -162,6 +164,38 @@ int rkfdBatchContactStats(rkfdBatch *b, int reset, double *mean_rigid, double *m
  * (reference src/rkfd_sim.c:277-287) and rkFDUpdateInit. */
 int rkfdBatchSnapshot(rkfdBatch *b);
 int rkfdBatchRestore(rkfdBatch *b, void *stream);
+
+/* ---- per-instance physical parameters (domain randomisation) --------------------------------------------------------
+ * A batch is `batch` copies of one world; these calls let every instance have its OWN link masses, centres of mass, inertias, joint
+ * friction and contact-info constants - what a caller of the reference gets by building one rkFD per world from its own chain
+ * and contact-info files.  Parameters are addressed in MODEL space (the links and contact infos of the rkfdModel the batch was made
+ * from, not the device's merged links), one key at a time, values[batch][width] instance-major.  Instance i of a batch that
+ * carries parameters P_i gives, bit for bit, what a plain batch gives on a copy of the model that holds P_i.
+ *   rkfdBatchSetParam: synchronous like rkfdBatchSetState - waits for the batch's launches (its internal streams and the stream of
+ *     its last launch; launches the caller spread over other streams of its own must be joined first), takes effect from the next
+ *     launch.  The first Set on a batch that runs a world-specific kernel (rkfdBatchSpecialize) also fetches the kernel built for
+ *     batches with a table: from the store `make spec` fills, else a run-time compile of a few seconds, once per world; a Set that
+ *     fails for any reason (-1) has changed nothing - neither the table nor the kernel in use.  It
+ *     touches no state: friction pivots, contact anchors and broken flags stay as they are.  values = NULL: this key back to the
+ *     model's value in every instance.  Refused with -1 and a message (rkfdHipLastError), the table left as it was: an unknown key, a
+ *     value that is not finite, a negative mass, a mass of 0 for a link whose mass is positive in the model.
+ *   rkfdBatchGetParam: what the next launch will use (the model's values if the key was never set).
+ *   rkfdBatchClearParams: every key back to the model; frees the table.  rkfdBatchHasParams: 1 while the batch carries a table.
+ * rkfdBatchSnapshot / rkfdBatchRestore neither save nor restore parameters: they are not state.  Every launch honours the table:
+ * rkfdBatchUpdateInit / Update / UpdateControlled(Dev) / Eval / Profile, whatever rkfdBatchSpecialize, SetSplit, SetStepsPerLaunch,
+ * SetInstancesPerWave or TuneInstancesPerWave chose (the tuning measures with the table in place and keeps it).
+ * Topology, geometry, joint types, motor constants, dt and the solver's settings stay per world (DEVIATIONS.md).
+ * Cost: 17 device links + 6 contact infos doubles per instance on the device (config 4: about 4 KB), the same again in model
+ * space on the host, allocated at the first Set. */
+enum { RKFD_PAR_MASS, RKFD_PAR_COM, RKFD_PAR_INERTIA,                            /* per link: 1, 3, 9 doubles */
+       RKFD_PAR_STIFF, RKFD_PAR_VISC, RKFD_PAR_COULOMB, RKFD_PAR_SFRIC,          /* per link: 1 each */
+       RKFD_PAR_CI_SF, RKFD_PAR_CI_KF, RKFD_PAR_CI_K, RKFD_PAR_CI_L, RKFD_PAR_CI_E, RKFD_PAR_CI_V,   /* per contact info */
+       RKFD_PAR_COUNT };
+int rkfdBatchParamWidth(const rkfdBatch *b, int which);                 /* doubles per instance: nlink*{1,3,9} or nci; -1: bad key */
+int rkfdBatchSetParam(rkfdBatch *b, int which, const double *values);   /* [batch][width]; NULL: this key back to the model's value */
+int rkfdBatchGetParam(rkfdBatch *b, int which, double *values);         /* what the next launch will use */
+int rkfdBatchClearParams(rkfdBatch *b);                                  /* all keys back to the model; frees the table */
+int rkfdBatchHasParams(const rkfdBatch *b);
 
 /* diagnostic launch: nsteps x rkFDUpdate with in-kernel phase stamps.  out is [batch][32]
   * (RKFD_NPROF = 32 per instance) shader-clock cycles: kinematics, collision+penalty, sweep 2, sweep 3 (both
@@ -221,6 +255,10 @@ int rkfdNodeStatus(rkfdNode *n);
 /* rkfdBatchUpdateControlled on every device: u is the host schedule of ALL instances, [total][nsteps][nlink]; each device's thread
  * copies its shard's contiguous block on the device's own stream, in order with its steps */
 int rkfdNodeUpdateControlled(rkfdNode *n, int nsteps, const double *u);
+/* rkfdBatchSetParam / rkfdBatchClearParams on every device: values is the host array of ALL instances, [total][width], sharded like
+ * rkfdNodeSetState (NULL: the key back to the model's value everywhere).  Nothing is changed on any device when one refuses. */
+int rkfdNodeSetParam(rkfdNode *n, int which, const double *values);
+int rkfdNodeClearParams(rkfdNode *n);
 /* one ncclAllGather of the final {dis, vel}: afterwards every device holds all `total` final states (rkfdNodeGatherDev: on
  * device k, [ndev][mx][2 ndof] doubles - block j = shard j's instances, dis | vel per instance, padded to the largest shard mx),
  * and dis / vel ([total][ndof], either may be NULL) receive them on the host in instance order */

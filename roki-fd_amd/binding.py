@@ -97,12 +97,16 @@ def lib():
     L.rkfdBatchSetStepsPerLaunch.argtypes = [vp, C.c_int]
     L.rkfdBatchTuneInstancesPerWave.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
     L.rkfdSpecializeCompileW.argtypes = [C.POINTER(RkfdModel), C.c_int, C.c_int]
+    L.rkfdSpecializeCompileP.argtypes = [C.POINTER(RkfdModel), C.c_int, C.c_int, C.c_int]
     L.rkfdBatchUpdateInit.argtypes = [vp, vp]
     L.rkfdBatchUpdate.argtypes = [vp, C.c_int, vp]
     L.rkfdBatchEval.argtypes = [vp, C.c_int, vp]
     L.rkfdBatchUpdateControlled.argtypes = [vp, C.c_int, vp, vp]; L.rkfdBatchUpdateControlledDev.argtypes = [vp, C.c_int, vp, vp]
     L.rkfdNodeUpdateControlled.argtypes = [vp, C.c_int, vp]
     L.rkfdLdsBytesFor.argtypes = [C.POINTER(RkfdModel), C.c_int]
+    L.rkfdBatchParamWidth.argtypes = [vp, C.c_int]; L.rkfdBatchSetParam.argtypes = [vp, C.c_int, vp]; L.rkfdBatchGetParam.argtypes = [vp, C.c_int, vp]
+    L.rkfdBatchClearParams.argtypes = [vp]; L.rkfdBatchHasParams.argtypes = [vp]
+    L.rkfdNodeSetParam.argtypes = [vp, C.c_int, vp]; L.rkfdNodeClearParams.argtypes = [vp]
     L.rkfdBatchStatus.argtypes = [vp, vp]
     L.rkfdBatchContactStats.argtypes = [vp, C.c_int, _pd, _pd, C.POINTER(C.c_longlong)]
     L.rkfdBatchSnapshot.argtypes = [vp]; L.rkfdBatchRestore.argtypes = [vp, vp]
@@ -202,6 +206,20 @@ class World:
         return buf[:n].copy()
 
 
+# per-instance physical parameters (include/rkfd_hip.h: RKFD_PAR_*): the key of a name is its place here
+PARAM_NAMES = ("mass", "com", "inertia", "stiff", "visc", "coulomb", "sfric", "ci_sf", "ci_kf", "ci_k", "ci_l", "ci_e", "ci_v")
+
+
+def param_key(name_or_key):
+    """key of a parameter given by name ("mass", "ci_kf", ...) or by key; an unknown NAME is a ValueError, an unknown integer
+    key goes to the library, which refuses it with a message"""
+    if isinstance(name_or_key, str):
+        if name_or_key not in PARAM_NAMES:
+            raise ValueError(f"unknown parameter {name_or_key!r}: one of {', '.join(PARAM_NAMES)}")
+        return PARAM_NAMES.index(name_or_key)
+    return int(name_or_key)
+
+
 class Batch:
     """B instances of one world on one GPU (include/rkfd_hip.h).  All arrays are
     instance-major numpy arrays [B, ...]."""
@@ -280,6 +298,41 @@ class Batch:
     def set_broken(self, broken):
         br = np.ascontiguousarray(broken, dtype=np.int32).reshape(self.B, self.nlink)
         self._synced(self._L.rkfdBatchSetBroken(self._b, _ptr(br)))
+
+    def param_width(self, name_or_key):
+        """doubles per instance of a parameter: nlink * {1, 3, 9} or nci (model space)"""
+        w = self._L.rkfdBatchParamWidth(self._b, param_key(name_or_key))
+        if w < 0:
+            raise RkfdError(f"unknown parameter key {name_or_key!r}")
+        return w
+
+    def set_param(self, name_or_key, values):
+        """per-instance physical parameters (rkfdBatchSetParam): values (B, width) in MODEL space - the links / contact infos of
+        the world the batch was made from -, None: this parameter back to the model's value.  Synchronous; takes effect from the
+        next launch; touches no state."""
+        k = param_key(name_or_key)
+        if values is None:
+            self._synced(self._L.rkfdBatchSetParam(self._b, k, None))
+            return
+        w = self._L.rkfdBatchParamWidth(self._b, k)
+        if w >= 0:
+            values = np.ascontiguousarray(values, dtype=np.float64).reshape(self.B, w)
+        else:
+            values = np.ascontiguousarray(values, dtype=np.float64)      # (the library refuses the key with its message)
+        self._synced(self._L.rkfdBatchSetParam(self._b, k, _ptr(values)))
+
+    def get_param(self, name_or_key):
+        """what the next launch will use, (B, width): the model's values where the parameter was never set"""
+        k = param_key(name_or_key)
+        out = np.empty((self.B, self.param_width(k)))
+        self._chk(self._L.rkfdBatchGetParam(self._b, k, _ptr(out)))
+        return out
+
+    def clear_params(self):
+        self._synced(self._L.rkfdBatchClearParams(self._b))
+
+    def has_params(self):
+        return bool(self._L.rkfdBatchHasParams(self._b))
 
     def update_init(self, stream=None):
         self._chk(self._L.rkfdBatchUpdateInit(self._b, stream))
@@ -455,6 +508,16 @@ class Node:
     def set_motor_input(self, inp):
         inp = np.ascontiguousarray(inp, dtype=np.float64).reshape(self.total, self.nlink)
         self._chk(self._L.rkfdNodeSetMotorInput(self._n, _ptr(inp)))
+
+    def set_param(self, name_or_key, values):
+        """Batch.set_param over all instances: values (total, width), sharded like set_state; None: back to the model's value"""
+        k = param_key(name_or_key)
+        if values is not None:
+            values = np.ascontiguousarray(values, dtype=np.float64).reshape(self.total, -1)
+        self._chk(self._L.rkfdNodeSetParam(self._n, k, _ptr(values) if values is not None else None))
+
+    def clear_params(self):
+        self._chk(self._L.rkfdNodeClearParams(self._n))
 
     def update_controlled(self, u):
         """Batch.update_controlled on every device: u is the host schedule of all instances, (total, H, nlink) float64"""

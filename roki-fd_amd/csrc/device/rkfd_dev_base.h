@@ -193,6 +193,27 @@ template<class T> RKFD_DEV const T *rkfd_reload(const T *p){ asm volatile( "" : 
 #  define RELOAD(p) rkfd_reload(p)
 #endif
 
+/* The physical parameters an instance may have of its own (rkfdBatchSetParam): link mass, centre of mass, inertia, joint friction and
+ * the contact infos' constants.  RKFD_PARAMS = 0 (the kernels of batches without a table): the model's arrays, read as ever.
+ * RKFD_PARAMS = 1 (rkfd_capi_par.hip, the world-specific kernels of batches with a table, the lane emulator's harness): the model's
+ * pointers to them point at the table's first row (the host swaps them in before the launch) and the instance reads L.pd doubles
+ * further on.  One instance per wavefront: L.pd is wave-uniform and goes into the scalar base.  Two: the halves read different
+ * rows, so the base stays the scalar one RELOAD's "+s" needs and the row is a per-lane integer offset.  RKFD_PARC: the same for
+ * the reads that were never re-loaded (the contact infos). */
+#ifndef RKFD_PARAMS
+#define RKFD_PARAMS 0
+#endif
+#if !RKFD_PARAMS
+#  define RKFD_PAR(L, p, i)   RELOAD( p )[i]
+#  define RKFD_PARC(L, p, i)  (p)[i]
+#elif RKFD_W == 1 && !defined(RKFD_EMU)
+#  define RKFD_PAR(L, p, i)   RELOAD( (p) + (L).pd )[i]
+#  define RKFD_PARC(L, p, i)  ( (p) + (L).pd )[i]
+#else
+#  define RKFD_PAR(L, p, i)   RELOAD( p )[(i) + (L).pd]
+#  define RKFD_PARC(L, p, i)  (p)[(i) + (L).pd]
+#endif
+
 /* optional in-kernel phase timing (diagnostic launches only: rkfdBatchProfile) */
 #define RKFD_NPROF 32
 #ifdef RKFD_EMU
@@ -417,6 +438,9 @@ typedef struct {
   /* grouped Gauss-Seidel (worlds with more than 16 rigid contact vertices): the layout of the last evaluation - per lane the two
    * moving trees of its contact (2 bytes), the position table (64 bytes), the row fills, the contact count (RKFD_GC_INTS ints) */
   int *GC;
+  /* per-instance physical parameters (rkfdBatchSetParam): doubles from the table's first row to this instance's row (kernels built
+   * with RKFD_PARAMS = 1 only) - set by rkfd_instance, not by rkfd_lds_carve; read through RKFD_PAR / RKFD_PARC */
+  int pd;
 } rkfdLds;
 RKFD_DEV void rkfd_lds_carve(rkfdLds *L, void *base, int NL, int ND, int NC, int M, int nlevel, int npool, int nfloat, int maxact, int nside, int pu_alias, int npurow, int vert_rigid, int has_slide, int ma_size,
                              int vol_np, int vol_ncp, int vol_pv, int vol_nf, int pyramid, int has_pl, void *shared = 0)

@@ -212,14 +212,14 @@ RKFD_DEV void d_modify_friction(const rkfdDevModel &m, const rkfdLds &L, int j, 
   const double fn = d_dot( f, ax );
   const double f1 = d_dot( f, ax+3 ), f2 = d_dot( f, ax+6 );
   const double fs = sqrt( f1*f1 + f2*f2 );
-  const double mu = L.typ[j] == RKFD_SF ? m.ci_sf[ci] : m.ci_kf[ci];
+  const double mu = L.typ[j] == RKFD_SF ? RKFD_PARC( L, m.ci_sf, ci ) : RKFD_PARC( L, m.ci_kf, ci );
   if( !( fabs( fs ) < RKFD_DEV_TOL ) && fs > mu*fn ){
     const double vn = d_dot( vr, ax );
     double v[3] = { vr[0]-vn*ax[0], vr[1]-vn*ax[1], vr[2]-vn*ax[2] };
     const double vs = sqrt( d_dot( v, v ) );
     f[0] = fn*ax[0]; f[1] = fn*ax[1]; f[2] = fn*ax[2];
     if( !( fabs( vs ) < RKFD_DEV_TOL ) ){
-      const double k = -( 1.0 - exp( -1.0*m.fric_w*vs ) )*m.ci_kf[ci]*fn/vs;
+      const double k = -( 1.0 - exp( -1.0*m.fric_w*vs ) )*RKFD_PARC( L, m.ci_kf, ci )*fn/vs;
       f[0] += k*v[0]; f[1] += k*v[1]; f[2] += k*v[2];
     }
     if( doUpRef ){
@@ -245,7 +245,7 @@ RKFD_DEV void rkfd_phase_penalty(const rkfdDevModel &m, const rkfdLds &L, bool d
     double va[3], vb[3], vr[3], f[3];
     d_point_vel( &L.V[6*RKFD_CI_A( cinf )], x, va );
     d_point_vel( &L.V[6*RKFD_CI_B( cinf )], x, vb );
-    const double E = m.ci_e[ci], kv = -1.0*( m.ci_v[ci] + E*m.dt );
+    const double E = RKFD_PARC( L, m.ci_e, ci ), kv = -1.0*( RKFD_PARC( L, m.ci_v, ci ) + E*m.dt );
 #pragma unroll
     for( int k=0; k<3; k++ ){
       vr[k] = va[k]-vb[k] + ( m.has_slide ? L.SV[3*L.asl[j]+k] : 0.0 );

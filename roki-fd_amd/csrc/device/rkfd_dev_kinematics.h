@@ -195,10 +195,10 @@ template<bool prof> RKFD_DEV void rkfd_phase_kinematics(const rkfdDevModel &m, c
       c[3] += t[0]; c[4] += t[1]; c[5] += t[2];
     }
     /* spatial inertia about the world origin and bias force */
-    const double ms = RELOAD( m.mass )[i];
+    const double ms = RKFD_PAR( L, m.mass, i );
     double cw[3], Iw[9], t9[9], Ic[9], RT[9] = { R[0],R[3],R[6], R[1],R[4],R[7], R[2],R[5],R[8] };
     {
-      const double *cm = &RELOAD( m.com )[3*i], *I0 = &RELOAD( m.inertia )[9*i];
+      const double *cm = &RKFD_PAR( L, m.com, 3*i ), *I0 = &RKFD_PAR( L, m.inertia, 9*i );
       double cl[3] = { cm[0], cm[1], cm[2] };
 #pragma unroll
       for( int k=0; k<9; k++ ) Ic[k] = I0[k];
@@ -260,11 +260,11 @@ template<bool prof> RKFD_DEV void rkfd_phase_kinematics(const rkfdDevModel &m, c
           treg = admit*gk*gk*qd1;
           tf = jm*( -qd1/m.dt ) - tin + treg + ll.pivp;
           double fmax;
-          if( ll.pivt == RKFD_SF ) fmax = RELOAD( m.sfric )[i];
+          if( ll.pivt == RKFD_SF ) fmax = RKFD_PAR( L, m.sfric, i );
           else {
             const double q = q1;      /* (L.q shares its storage with PB / C, written above) */
             const double sg = qd1 > 0 ? 1.0 : ( qd1 < 0 ? -1.0 : 0.0 );
-            fmax = -RELOAD( m.stiff )[i]*q - RELOAD( m.visc )[i]*qd1 - RELOAD( m.coulomb )[i]*sg;
+            fmax = -RKFD_PAR( L, m.stiff, i )*q - RKFD_PAR( L, m.visc, i )*qd1 - RKFD_PAR( L, m.coulomb, i )*sg;
           }
           fmax = fabs( fmax );
           int newt;

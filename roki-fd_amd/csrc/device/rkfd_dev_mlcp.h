@@ -346,7 +346,7 @@ template<bool pk> RKFD_DEV void rkfd_pgs_grouped(const rkfdDevModel &m, const rk
     i1 = fabs( d1 ) < RKFD_DEV_TOL ? 0.0 : 1.0/d1;
     i2 = fabs( d2 ) < RKFD_DEV_TOL ? 0.0 : 1.0/d2;
     const int jr_ = L.lrg[k], cir_ = RKFD_CI_CI( L.CIp[jr_] );
-    mu = L.typ[jr_] == RKFD_SF ? m.ci_sf[cir_] : m.ci_kf[cir_];
+    mu = L.typ[jr_] == RKFD_SF ? RKFD_PARC( L, m.ci_sf, cir_ ) : RKFD_PARC( L, m.ci_kf, cir_ );
   }
   SYNC();       /* (MF shares its storage with MB in these kernels: everybody has read b before anybody writes f) */
   for( int it=0; it<m.max_iter; it++ ){
@@ -436,7 +436,7 @@ RKFD_DEV void rkfd_pgs_grouped_sw(const rkfdDevModel &m, const rkfdLds &L, const
     i1 = fabs( d1 ) < RKFD_DEV_TOL ? 0.0 : 1.0/d1;
     i2 = fabs( d2 ) < RKFD_DEV_TOL ? 0.0 : 1.0/d2;
     const int jr_ = L.lrg[k], cir_ = RKFD_CI_CI( L.CIp[jr_] );
-    mu = L.typ[jr_] == RKFD_SF ? m.ci_sf[cir_] : m.ci_kf[cir_];
+    mu = L.typ[jr_] == RKFD_SF ? RKFD_PARC( L, m.ci_sf, cir_ ) : RKFD_PARC( L, m.ci_kf, cir_ );
   }
   SYNC();       /* (MF shares its storage with MB in these kernels: everybody has read b before anybody writes f) */
   for( int it=0; it<m.max_iter; it++ ){
@@ -603,8 +603,8 @@ template<bool prof, bool vqp, bool pk> RKFD_DEV void rkfd_phase_mlcp(const rkfdD
       ra[k] = ( L.AC[6*la+3+k] + ta[k] ) - ( L.AC[6*lb+3+k] + tb[k] );
       d[k] = x[k]-L.RW[3*L.asl[j]+k];
     }
-    const double mu = L.typ[j] == RKFD_SF ? m.ci_sf[ci] : m.ci_kf[ci];
-    const double K = m.ci_k[ci];
+    const double mu = L.typ[j] == RKFD_SF ? RKFD_PARC( L, m.ci_sf, ci ) : RKFD_PARC( L, m.ci_kf, ci );
+    const double K = RKFD_PARC( L, m.ci_k, ci );
     double axl[9];
     d_load_axes( L, L.asl[j], axl );
 #pragma unroll
@@ -801,7 +801,7 @@ template<bool prof, bool vqp, bool pk> RKFD_DEV void rkfd_phase_mlcp(const rkfdD
       }
       if( cr == ck && !vert ){
         /* relaxation on the diagonal */
-        const double rl = m.ci_l[RKFD_CI_CI( L.CIp[L.lrg[cr]] )];
+        const double rl = RKFD_PARC( L, m.ci_l, RKFD_CI_CI( L.CIp[L.lrg[cr]] ) );
         blk[0] += rl; blk[4] += rl; blk[8] += rl;
       }
       if( sw ){
@@ -883,7 +883,7 @@ template<bool prof, bool vqp, bool pk> RKFD_DEV void rkfd_phase_mlcp(const rkfdD
       i1 = fabs( d1 ) < RKFD_DEV_TOL ? 0.0 : 1.0/d1;
       i2 = fabs( d2 ) < RKFD_DEV_TOL ? 0.0 : 1.0/d2;
       const int jr_ = L.lrg[lane], cir_ = RKFD_CI_CI( L.CIp[jr_] );
-      mu = L.typ[jr_] == RKFD_SF ? m.ci_sf[cir_] : m.ci_kf[cir_];
+      mu = L.typ[jr_] == RKFD_SF ? RKFD_PARC( L, m.ci_sf, cir_ ) : RKFD_PARC( L, m.ci_kf, cir_ );
     }
     /* up to 4 contacts: the lane's matrix rows in registers; up to 16: increments broadcast through the DPP operand of
      * the FMA; more, or the packed matrix (worlds with more than 16 contacts; its index arithmetic in four-contact
@@ -923,7 +923,7 @@ template<bool prof, bool vqp, bool pk> RKFD_DEV void rkfd_phase_mlcp(const rkfdD
     }
     { const int sl_ = L.asl[j]; L.CF[3*sl_] = fw[0]; L.CF[3*sl_+1] = fw[1]; L.CF[3*sl_+2] = fw[2]; L.FS[sl_] = 1; }
     const double fn = fw[0], fs = sqrt( fw[1]*fw[1] + fw[2]*fw[2] );
-    const double mu = L.typ[j] == RKFD_SF ? m.ci_sf[ci] : m.ci_kf[ci];
+    const double mu = L.typ[j] == RKFD_SF ? RKFD_PARC( L, m.ci_sf, ci ) : RKFD_PARC( L, m.ci_kf, ci );
     if( fs > mu*fn - RKFD_DEV_TOL ){
       L.typ[j] = RKFD_KF;
       { const int ri = RIDX( j ), sl_ = L.asl[j]; L.REF[3*ri] = L.PRO[3*sl_]; L.REF[3*ri+1] = L.PRO[3*sl_+1]; L.REF[3*ri+2] = L.PRO[3*sl_+2]; }

@@ -137,9 +137,13 @@ RKFD_DEV void rkfd_cat_dis(const rkfdDevModel &m, const rkfdLds &L, int dofkind,
  * s*nlink_model + model link] is the motor input of step s of this launch - rkJointMotorSetInput before each rkFDUpdate.  It holds
  * for the four Runge-Kutta-Gill stages and the committing evaluation of its step; the last step's input is stored to st.motor_in
  * (for the model links the device simulates - a link merged into its parent has no motor the device reads). */
+/* par_stride (kernels built with RKFD_PARAMS = 1 only; ignored otherwise): doubles of one row of the table of per-instance physical parameters
+ * (rkfdBatchSetParam).  The table needs no pointer of its own: with one the model's mass .. sfric and ci_sf .. ci_v point at its
+ * first row, and instance b reads b*par_stride doubles further on (RKFD_PAR, rkfd_dev_base.h).  A stand-in half has the index of
+ * the instance it repeats, and so that instance's row. */
 template<bool prof, int vqp, bool pk> RKFD_DEV void rkfd_instance(const rkfdDevModel &m_, const rkfdDevState &st, int b, void *ldsbase,
                             int mode, int nsteps, int *errflag, bool live = true, void * /* ignored: the LDS behind the instances' blocks (lds_shared, now 0); the lane emulator still passes it */ = 0,
-                            const double *ctrl = nullptr, int ctrl_stride = 0)
+                            const double *ctrl = nullptr, int ctrl_stride = 0, int par_stride = 0)
 {
 #ifdef RKFD_SPEC
   /* kernel compiled for ONE world (rkfdBatchSpecialize, hipRTC): its dimensions are literals, so the LDS layout,
@@ -169,6 +173,7 @@ template<bool prof, int vqp, bool pk> RKFD_DEV void rkfd_instance(const rkfdDevM
   rkfdLds L;
   rkfd_lds_carve( &L, ldsbase, NL, ND, NC, 3*m.maxrg, m.nlevel, m.npool, m.nfloat, m.maxact, m.nside, m.pu_alias, m.npurow, m.vert_rigid, m.has_slide, m.ma_size,
                   vqp == 2 ? m.vol_np : 0, m.vol_ncp, m.vol_pv, m.vol_nf, m.pyramid, m.maxrg > 0, gtab ? (void *)m.tabs : 0 );
+  L.pd = RKFD_PARAMS ? b*par_stride : 0;
   if( m.lds_poison > 0 ){      /* (RKFD_DEBUG_POISON_LDS: see rkfd_devmodel.h) */
     for( int i=lane; i<m.lds_poison; i+=RKFD_WL ) ( (unsigned *)ldsbase )[i] = 0xffffffffu;
     SYNC();

@@ -246,7 +246,7 @@ template<bool prof> RKFD_DEV unsigned long long rkfd_vert_qp(const rkfdDevModel 
   {
     const double PI = 3.14159265358979323846;
     const int jc = L.lrg[cc], ci = RKFD_CI_CI( L.CIp[jc] );
-    const double mu = L.typ[jc] == RKFD_KF ? m.ci_kf[ci] : m.ci_sf[ci];
+    const double mu = L.typ[jc] == RKFD_KF ? RKFD_PARC( L, m.ci_kf, ci ) : RKFD_PARC( L, m.ci_sf, ci );
     double s0, c0, s1, c1;
     /* d_sincos takes any argument; the reference evaluates sin/cos of th+offset with th accumulated by additions */
     double th = 0.0;
@@ -274,7 +274,7 @@ template<bool prof> RKFD_DEV unsigned long long rkfd_vert_qp(const rkfdDevModel 
     SYNC();
     for( int t0=0; t0<n*n; t0+=RKFD_WAVE ){
       const int t = t0 + lane, i = t/n, k = t - i*n;
-      if( t < n*n && k <= i ) Q[RKFD_QI( i, k )] = W[i*ldq+k] + ( i == k ? m.ci_l[RKFD_CI_CI( L.CIp[L.lrg[i/3]] )] : 0.0 );
+      if( t < n*n && k <= i ) Q[RKFD_QI( i, k )] = W[i*ldq+k] + ( i == k ? RKFD_PARC( L, m.ci_l, RKFD_CI_CI( L.CIp[L.lrg[i/3]] ) ) : 0.0 );
     }
     SYNC();
   } else
@@ -285,7 +285,7 @@ template<bool prof> RKFD_DEV unsigned long long rkfd_vert_qp(const rkfdDevModel 
       double s = 0;
 #pragma unroll 8
       for( int r=0; r<n; r++ ) s = fma( L.MA[r*ld+i], L.MA[r*ld+k], s );
-      if( i == k ) s += m.ci_l[RKFD_CI_CI( L.CIp[L.lrg[i/3]] )];
+      if( i == k ) s += RKFD_PARC( L, m.ci_l, RKFD_CI_CI( L.CIp[L.lrg[i/3]] ) );
       Q[RKFD_QI( i, k )] = s;
     }
   }
@@ -576,7 +576,7 @@ template<bool prof> RKFD_DEV void rkfd_vert_qp_wide(const rkfdDevModel &m, const
     for( int q=lane; q<mc; q+=RKFD_WAVE ){
       const int cc = q/P, kf = q - cc*P;
       const int jc = L.lrg[cc], ci = RKFD_CI_CI( L.CIp[jc] );
-      const double mu = L.typ[jc] == RKFD_KF ? m.ci_kf[ci] : m.ci_sf[ci];
+      const double mu = L.typ[jc] == RKFD_KF ? RKFD_PARC( L, m.ci_kf, ci ) : RKFD_PARC( L, m.ci_sf, ci );
       double th = 0.0, s1, c1;
       for( int k=0; k<kf; k++ ) th += 2.0*PI/P;
       d_sincos( th + ( -PI/P ), &s1, &c1 );
@@ -595,7 +595,7 @@ template<bool prof> RKFD_DEV void rkfd_vert_qp_wide(const rkfdDevModel &m, const
     if( k <= i ){
       double s = 0;
       for( int r=0; r<n; r++ ) s = fma( L.MA[r*ld+i], L.MA[r*ld+k], s );
-      if( i == k ) s += m.ci_l[RKFD_CI_CI( L.CIp[L.lrg[i/3]] )];
+      if( i == k ) s += RKFD_PARC( L, m.ci_l, RKFD_CI_CI( L.CIp[L.lrg[i/3]] ) );
       Q[RKFD_QI( i, k )] = s;
     }
   }

@@ -392,7 +392,7 @@ template<bool prof> RKFD_DEV void rkfd_phase_volcol(const rkfdDevModel &m, const
 #pragma unroll
     for( int k=0; k<RKFD_VOL_NRED; k++ ) val[k] = 0;
     {
-      const double K = m.ci_k[ci];
+      const double K = RKFD_PARC( L, m.ci_k, ci );
       for( int i=1; i+1<n; i++ ){
         const double tri[9] = { P[0], P[1], P[2], P[3*i], P[3*i+1], P[3*i+2], P[3*i+3], P[3*i+4], P[3*i+5] };
         const double e1[3] = { tri[3]-tri[0], tri[4]-tri[1], tri[5]-tri[2] }, e2[3] = { tri[6]-tri[0], tri[7]-tri[1], tri[8]-tri[2] };
@@ -945,7 +945,7 @@ RKFD_DEV int rkfd_vol_friction(const rkfdDevModel &m, const rkfdLds &L, int k, i
     /* _rkFDSolverPlaneVertSlideDir (:759-776) */
     const double t1 = c2[6], t2 = c2[7], nv = sqrt( t1*t1 + t2*t2 );
     if( !( fabs( nv ) < RKFD_DEV_TOL ) ){
-      const double ww = ( 1.0 - exp( -1.0*m.fric_w*nv ) )*m.ci_kf[ci]/nv;
+      const double ww = ( 1.0 - exp( -1.0*m.fric_w*nv ) )*RKFD_PARC( L, m.ci_kf, ci )/nv;
       sx = -ww*t1; sy = -ww*t2;
     }
   }
@@ -953,7 +953,7 @@ RKFD_DEV int rkfd_vol_friction(const rkfdDevModel &m, const rkfdLds &L, int k, i
     int mr, n;
     if( stage == 1 ){
       /* _rkFDSolverModifyWrenchStaticConstraint (:652-675) */
-      const double mu = m.ci_sf[ci];
+      const double mu = RKFD_PARC( L, m.ci_sf, ci );
       mr = 6; n = P*ncp;
       for( int j=lane; j<n; j+=RKFD_WAVE ){
         const int kk = j/P, i = j - kk*P;
@@ -1158,7 +1158,7 @@ template<bool prof> RKFD_DEV void rkfd_phase_volume(const rkfdDevModel &m, const
         }
         if( k == n ) cvq[r] = acc;
         else {
-          if( k == r ) acc += m.ci_l[RKFD_VP_CI( &RELOAD( m.vol_pair )[8*L.VI[2*( r/6 )+1]] )];
+          if( k == r ) acc += RKFD_PARC( L, m.ci_l, RKFD_VP_CI( &RELOAD( m.vol_pair )[8*L.VI[2*( r/6 )+1]] ) );
           L.VQL[RKFD_QI( r, k )] = acc;
         }
       }
@@ -1270,7 +1270,7 @@ template<bool prof> RKFD_DEV void rkfd_phase_volume(const rkfdDevModel &m, const
     double w[6];
 #pragma unroll
     for( int i=0; i<3; i++ ){ w[i] = d_dot( wr, ax+3*i ); w[i+3] = d_dot( wr+3, ax+3*i ); }
-    const double fn = w[0], fs = sqrt( w[1]*w[1] + w[2]*w[2] ), sf = m.ci_sf[ci];
+    const double fn = w[0], fs = sqrt( w[1]*w[1] + w[2]*w[2] ), sf = RKFD_PARC( L, m.ci_sf, ci );
     double tl = 0;
     for( int k=0; k<ncp; k++ ){
       const double *c2 = &L.VPL[8*( NCP*p + k )];
@@ -1285,7 +1285,7 @@ template<bool prof> RKFD_DEV void rkfd_phase_volume(const rkfdDevModel &m, const
         const double t1 = vd[RKFD_VD_TC], t2 = vd[RKFD_VD_TC+1], nv = sqrt( t1*t1 + t2*t2 );
         if( fabs( nv ) < RKFD_DEV_TOL ){ w[1] = w[2] = 0; }
         else {
-          const double t = ( 1.0 - exp( -1.0*m.fric_w*nv ) )*m.ci_kf[ci]*w[0]/nv;
+          const double t = ( 1.0 - exp( -1.0*m.fric_w*nv ) )*RKFD_PARC( L, m.ci_kf, ci )*w[0]/nv;
           w[1] = -t*t1; w[2] = -t*t2;
         }
         kin = 1;

@@ -24,6 +24,12 @@ static thread_local char g_err[512] = "";
 #define HIPCHK(call, ret) do{ hipError_t e_ = (call); if( e_ != hipSuccess ){ \
   SETERR( "%s failed: %s", #call, hipGetErrorString( e_ ) ); return ret; } }while(0)
 
+/* Per-instance physical parameters (rkfdBatchSetParam): a batch that carries a table launches a SECOND set of step kernels, the same
+ * device code compiled with RKFD_PARAMS = 1 (rkfd_capi_par.hip, a translation unit of its own; the world-specific kernel likewise),
+ * which take the doubles of one table row as a ninth argument and read the parameters at the instance's row (RKFD_PAR in
+ * rkfd_dev_base.h); the model `m` such a launch passes has its mass .. sfric and ci_sf .. ci_v pointing at the table's first row
+ * (par_model below).  The kernels of this file are what they were before the table existed, instruction for instruction: a batch
+ * without a table pays nothing for the feature. */
 /* one workgroup = one wavefront = one world instance; state lives in LDS for the whole launch.
  * Register budget: the kernels need ~150-160 VGPRs when built with -mllvm -disable-machine-licm (see Makefile):
  * three waves per SIMD, i.e. up to twelve instances per CU where the LDS allows (10 for the humanoid worlds).
@@ -94,6 +100,9 @@ rkfd_restore_kernel(rkfdDevState st, rkfdDevState sn, int first, int ND, int NLM
 }
 
 typedef void (*rkfdKernel)(rkfdDevModel, rkfdDevState, int, int, int, int *, const double *, int);
+typedef void (*rkfdKernelPar)(rkfdDevModel, rkfdDevState, int, int, int, int *, const double *, int, int);
+/* rkfd_capi_par.hip: the step kernel built with RKFD_PARAMS = 1 - kind 0 plain, 1 packed matrix, 2 Vert QP, 3 Volume */
+extern "C" rkfdKernelPar rkfd_par_kernel(int kind, int prof);
 #define RKFD_MAX_SPLIT 8
 
 struct rkfdBatch {
@@ -108,9 +117,12 @@ struct rkfdBatch {
   size_t lds_bytes;
   size_t lds_pad;         /* RKFD_LDS_PAD_BYTES (diagnostic): extra LDS every workgroup asks for, one instance per wavefront or two */
   rkfdKernel kern, kern_prof;
+  rkfdKernelPar kern_par, kern_prof_par;      /* the same with a table of per-instance parameters */
   /* rkfdBatchSpecialize: the step kernel compiled for this world (hipRTC); NULL = the generic kernels above */
   hipModule_t spec_mod;
   hipFunction_t spec_fn;
+  hipStream_t last_stream;   /* the caller's stream of the last launch: what rkfdBatchSetParam / ClearParams wait for besides the internal streams */
+  int spec_par;              /* 1: spec_fn was compiled with RKFD_PARAMS = 1 (the batch carried a table when it was made) */
   /* rkfdBatchSetInstancesPerWave( b, 2 ): a second device model (sweep schedule with four links per iteration) for the
    * world-specific kernel built with RKFD_W = 2 - two instances per wavefront, 32 lanes each */
   int steps_per_launch;      /* under split launches: steps one launch carries (rkfdBatchSetStepsPerLaunch) */
@@ -136,6 +148,12 @@ struct rkfdBatch {
   size_t ctrl_cap;                   /* doubles */
   hipEvent_t ctrl_ev[RKFD_MAX_SPLIT];
   int ctrl_nev;                      /* events of ctrl_ev recorded by the last call */
+  /* rkfdBatchSetParam: the host copy in MODEL space, h_par[key][batch][width] (allocated by the first Set, initialised from the
+   * model), and the device table rebuilt from it on every Set: one contiguous row of par_stride doubles per instance, the device
+   * links' mass | com | inertia | stiff | visc | coulomb | sfric, then ci_sf .. ci_v (rkfd_devmodel_par_row).  d_par == NULL: no table */
+  double *h_par[RKFD_PAR_COUNT];
+  double *d_par;
+  int par_stride;
 };
 
 extern "C" const char *rkfdHipLastError(void){ return g_err; }
@@ -210,9 +228,15 @@ extern "C" rkfdBatch *rkfdBatchCreate(const rkfdModel *m, int batch, int device,
   b->kern = b->dm.vert_rigid ? rkfd_step_kernel_vqp : ( b->dm.ma_packed ? rkfd_step_kernel_pk : rkfd_step_kernel );
   b->kern_prof = b->dm.vert_rigid ? rkfd_step_kernel_prof_vqp : ( b->dm.ma_packed ? rkfd_step_kernel_prof_pk : rkfd_step_kernel_prof );
   if( b->dm.vol_np > 0 ){ b->kern = rkfd_step_kernel_vol; b->kern_prof = rkfd_step_kernel_prof_vol; }
+  {
+    const int kind = b->dm.vol_np > 0 ? 3 : ( b->dm.vert_rigid ? 2 : ( b->dm.ma_packed ? 1 : 0 ) );
+    b->kern_par = rkfd_par_kernel( kind, 0 ); b->kern_prof_par = rkfd_par_kernel( kind, 1 );
+  }
   if( b->lds_bytes > 64*1024 ){
     hipError_t e = hipFuncSetAttribute( (const void *)b->kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes );
     if( e == hipSuccess ) e = hipFuncSetAttribute( (const void *)b->kern_prof, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes );
+    if( e == hipSuccess ) e = hipFuncSetAttribute( (const void *)b->kern_par, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes );
+    if( e == hipSuccess ) e = hipFuncSetAttribute( (const void *)b->kern_prof_par, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes );
     if( e != hipSuccess ){ SETERR( "hipFuncSetAttribute(LDS=%zu) failed: %s", b->lds_bytes, hipGetErrorString( e ) ); rkfdBatchDestroy( b ); return NULL; }
   }
   return b;
@@ -236,6 +260,7 @@ extern "C" void rkfdBatchDestroy(rkfdBatch *b)
   for( int k=0; k<b->ctrl_nev; k++ ) (void)hipEventSynchronize( b->ctrl_ev[k] );
   for( int k=0; k<RKFD_MAX_SPLIT; k++ ) if( b->ctrl_ev[k] ) (void)hipEventDestroy( b->ctrl_ev[k] );
   (void)hipFree( b->d_ctrl ); if( b->h_ctrl ) (void)hipHostFree( b->h_ctrl );
+  (void)hipFree( b->d_par ); for( int k=0; k<RKFD_PAR_COUNT; k++ ) free( b->h_par[k] );
   if( b->spec_mod ) (void)hipModuleUnload( b->spec_mod );
   (void)hipFree( b->d_err ); (void)hipFree( b->dblob ); (void)hipFree( b->dblob2 );
   rkfd_devmodel_free( &b->host ); rkfd_devmodel_free( &b->host2 );
@@ -418,26 +443,41 @@ static int sync_streams(rkfdBatch *b)
   b->pending = 0;
   return 0;
 }
+/* the device model a launch passes: with a table of per-instance parameters, the pointers to those parameters point at its first
+ * row (the layout of rkfd_devmodel_par_row); both device models of a batch have the same device links */
+static rkfdDevModel par_model(const rkfdBatch *b, const rkfdDevModel &dm)
+{
+  rkfdDevModel d = dm;
+  if( b->d_par ) rkfd_devmodel_par_bind( &d, b->d_par );
+  return d;
+}
 /* one kernel launch over `count` instances starting at `first`: the kernel compiled for this world when there is one */
 /* ctrl / ctrl_stride: the control schedule of this launch's first step (NULL: the motor input in the state holds) */
 static int launch_one(rkfdBatch *b, rkfdKernel kern, int count, int first, int mode, int nsteps, hipStream_t stream,
                       const double *ctrl = NULL, int ctrl_stride = 0)
 {
+  /* (a world-specific kernel always matches the batch: rkfdBatchSetParam / ClearParams rebuild it when the table comes or goes) */
+  int pstride = b->d_par ? b->par_stride : 0;
   if( b->spec_fn && !b->st.prof ){
+    rkfdDevModel dmp = par_model( b, b->ipw == 2 ? b->dm2 : b->dm );
     if( b->ipw == 2 ){
       /* two instances per wavefront: half as many workgroups, each with the LDS of two instances; the kernel learns where the
        * part ends through st.batch (a half beyond it is a stand-in that stores nothing) */
       rkfdDevState st2 = b->st;
       st2.batch = first + count;
-      void *args[] = { &b->dm2, &st2, &first, &mode, &nsteps, &b->d_err, &ctrl, &ctrl_stride };
+      void *args[] = { &dmp, &st2, &first, &mode, &nsteps, &b->d_err, &ctrl, &ctrl_stride, &pstride };      /* (the ninth: kernels with a table only) */
       HIPCHK( hipModuleLaunchKernel( b->spec_fn, ( count+1 )/2, 1, 1, RKFD_WAVE, 1, 1, (unsigned)wg2_bytes( b ), stream, args, NULL ), -1 );
       return 0;
     }
-    void *args[] = { &b->dm, &b->st, &first, &mode, &nsteps, &b->d_err, &ctrl, &ctrl_stride };
+    void *args[] = { &dmp, &b->st, &first, &mode, &nsteps, &b->d_err, &ctrl, &ctrl_stride, &pstride };
     HIPCHK( hipModuleLaunchKernel( b->spec_fn, count, 1, 1, RKFD_WAVE, 1, 1, (unsigned)b->lds_bytes, stream, args, NULL ), -1 );
     return 0;
   }
-  hipLaunchKernelGGL( kern, dim3( count ), dim3( RKFD_WAVE ), b->lds_bytes, stream, b->dm, b->st, first, mode, nsteps, b->d_err, ctrl, ctrl_stride );
+  if( b->d_par ){
+    rkfdKernelPar kp = kern == b->kern_prof ? b->kern_prof_par : b->kern_par;
+    hipLaunchKernelGGL( kp, dim3( count ), dim3( RKFD_WAVE ), b->lds_bytes, stream, par_model( b, b->dm ), b->st, first, mode, nsteps, b->d_err, ctrl, ctrl_stride, pstride );
+  }
+  else hipLaunchKernelGGL( kern, dim3( count ), dim3( RKFD_WAVE ), b->lds_bytes, stream, b->dm, b->st, first, mode, nsteps, b->d_err, ctrl, ctrl_stride );
   HIPCHK( hipGetLastError(), -1 );
   return 0;
 }
@@ -459,6 +499,7 @@ static int launch(rkfdBatch *b, int mode, int nsteps, void *stream, const double
   if( !b ){ SETERR( "null batch" ); return -1; }
   HIPCHK( hipSetDevice( b->device ), -1 );
   rkfdKernel kern = b->st.prof ? b->kern_prof : b->kern;
+  b->last_stream = (hipStream_t)stream;
   const int cstride = ctrl ? nsteps*b->nlink : 0;
   if( b->nsplit <= 1 || b->st.prof ){
     if( b->st.prof && sync_streams( b ) < 0 ) return -1;
@@ -502,11 +543,11 @@ static int launch(rkfdBatch *b, int mode, int nsteps, void *stream, const double
 }
 /* ---- the step kernel compiled for one world (hipRTC) ---------------------------------------------------- */
 /* source of the specialised kernel: the dimensions of the world as literals in front of the same device code */
-static std::string spec_source(const rkfdDevModel &d, int ipw = 1)
+static std::string spec_source(const rkfdDevModel &d, int ipw = 1, int par = 0)
 {
   char buf[4096];
   snprintf( buf, sizeof(buf),
-    "#define RKFD_SPEC 1\n#define RKFD_W %d\n"
+    "#define RKFD_SPEC 1\n#define RKFD_W %d\n%s"
     "#define RKFD_SPEC_NLINK %d\n#define RKFD_SPEC_NDOF %d\n#define RKFD_SPEC_NCAND %d\n#define RKFD_SPEC_NLINK_MODEL %d\n"
     "#define RKFD_SPEC_NLEVEL %d\n#define RKFD_SPEC_NROUND %d\n#define RKFD_SPEC_NSCHED %d\n#define RKFD_SPEC_MAXRG %d\n"
     "#define RKFD_SPEC_NPOOL %d\n#define RKFD_SPEC_NFLOAT %d\n#define RKFD_SPEC_MAXACT %d\n#define RKFD_SPEC_NSIDE %d\n"
@@ -517,19 +558,20 @@ static std::string spec_source(const rkfdDevModel &d, int ipw = 1)
     "#define RKFD_SPEC_VOL_NPAIR %d\n#define RKFD_SPEC_VOL_NP %d\n#define RKFD_SPEC_VOL_NCP %d\n#define RKFD_SPEC_VOL_PV %d\n#define RKFD_SPEC_VOL_NF %d\n"
     "#include \"rkfd_device.h\"\n"
     "extern \"C\" __global__ void __launch_bounds__(64, %d)\n"
-    "rkfd_step_kernel_spec(rkfdDevModel m, rkfdDevState st, int first, int mode, int nsteps, int *errflag, const double *ctrl, int ctrl_stride)\n"
+    "rkfd_step_kernel_spec(rkfdDevModel m, rkfdDevState st, int first, int mode, int nsteps, int *errflag, const double *ctrl, int ctrl_stride%s)\n"
     "{\n"
     "  extern __shared__ __attribute__((aligned(16))) char lds[];\n"
     "  int b = first + (int)blockIdx.x*RKFD_W + HALF();\n"
     "  if( RKFD_W == 1 && b >= st.batch ) return;\n"
     "  const bool live = b < st.batch;\n"
     "  if( !live ) b -= 1;\n"
-    "  rkfd_instance<false, %s, %s>( m, st, b, lds + HALF()*RKFD_SPEC_LDS_INSTANCE, mode, nsteps, errflag, live, nullptr, ctrl, ctrl_stride );\n"
+    "  rkfd_instance<false, %s, %s>( m, st, b, lds + HALF()*RKFD_SPEC_LDS_INSTANCE, mode, nsteps, errflag, live, nullptr, ctrl, ctrl_stride%s );\n"
     "}\n",
-    ipw, d.nlink, d.ndof, d.ncand, d.nlink_model, d.nlevel, d.nround, d.nsched, d.maxrg, d.npool, d.nfloat, d.maxact, d.nside,
+    ipw, par ? "#define RKFD_PARAMS 1\n" : "", d.nlink, d.ndof, d.ncand, d.nlink_model, d.nlevel, d.nround, d.nsched, d.maxrg, d.npool, d.nfloat, d.maxact, d.nside,
     d.npurow, d.pu_d0, d.pu_alias, d.vert_rigid, d.qscr_alias, d.has_slide, d.ma_size, d.ma_packed, d.max_iter, d.solver, d.pyramid, d.anchor, d.mlcp_mfma,
     d.has_brf, d.lds_instance, d.vol_npair, d.vol_np, d.vol_ncp, d.vol_pv, d.vol_nf,
-    ( d.vol_np > 0 || ipw == 2 || d.vert_rigid == 2 ) ? 2 : 3, d.vol_np > 0 ? "2" : ( d.vert_rigid ? "1" : "0" ), d.ma_packed ? "true" : "false" );
+    ( d.vol_np > 0 || ipw == 2 || d.vert_rigid == 2 ) ? 2 : 3, par ? ", int par_stride" : "", d.vol_np > 0 ? "2" : ( d.vert_rigid ? "1" : "0" ), d.ma_packed ? "true" : "false",
+    par ? ", par_stride" : "" );
   std::string src;
   if( const char *pre = getenv( "RKFD_SPEC_DEFINE" ) ){      /* diagnostic: NAME[,NAME...] defined as 1 in front of the source */
     std::string names( pre ); size_t p0 = 0;
@@ -658,9 +700,9 @@ static int g_spec_last_from_store = 0;      /* diagnostic: did the last spec_com
 extern "C" int rkfdSpecializeLastFromStore(void){ return g_spec_last_from_store; }
 
 /* compile for gfx950 from the sources the library carries (rkfd_device_src.inc): nothing is read from disk but the store above */
-static int spec_compile(const rkfdDevModel &d, std::vector<char> &code, int ipw = 1)
+static int spec_compile(const rkfdDevModel &d, std::vector<char> &code, int ipw = 1, int par = 0)
 {
-  const std::string src = spec_source( d, ipw );
+  const std::string src = spec_source( d, ipw, par );
   const char *opts[] = { "--offload-arch=gfx950", "-O3", "-Wno-unused-value", "-mllvm", "-disable-machine-licm" };
   const int nopts = (int)( sizeof(opts)/sizeof(opts[0]) );
   const unsigned long long key = spec_key( src, opts, nopts );
@@ -719,35 +761,37 @@ static int spec_compile(const rkfdDevModel &d, std::vector<char> &code, int ipw 
   if( rtc->priv ) spec_to_store( key, code );      /* (only what the compiler this library was built with produced: the private namespace) */
   return 0;
 }
-extern "C" int rkfdSpecializeCompileW(const rkfdModel *m, int max_rigid, int ipw)
+extern "C" int rkfdSpecializeCompileP(const rkfdModel *m, int max_rigid, int ipw, int par)
 {
   rkfdDevModelHost h;
   char err[256];
   if( ipw != 1 && ipw != 2 ){ SETERR( "rkfdSpecializeCompileW: 1 or 2 instances per wavefront" ); return -1; }
   if( !m || rkfd_devmodel_build_w( m, max_rigid, ipw == 2 ? 4 : 8, &h, err, sizeof(err) ) < 0 ){ SETERR( "rkfdSpecializeCompile: %s", m ? err : "null model" ); return -1; }
   std::vector<char> code;
-  const int r = spec_compile( h.dm, code, ipw );
+  const int r = spec_compile( h.dm, code, ipw, par ? 1 : 0 );
   rkfd_devmodel_free( &h );
   return r < 0 ? -1 : (int)code.size();
 }
+extern "C" int rkfdSpecializeCompileW(const rkfdModel *m, int max_rigid, int ipw){ return rkfdSpecializeCompileP( m, max_rigid, ipw, 0 ); }
 extern "C" int rkfdSpecializeCompile(const rkfdModel *m, int max_rigid){ return rkfdSpecializeCompileW( m, max_rigid, 1 ); }
-extern "C" int rkfdBatchSpecialize(rkfdBatch *b)
+/* the world-specific kernel of the batch as it is set up (instances per wavefront), without (par = 0) or with a table of
+ * per-instance parameters: compiled or taken from the store, loaded, checked - the batch itself is not touched */
+static int spec_build(rkfdBatch *b, int par, hipModule_t *mod, hipFunction_t *fn)
 {
-  if( !b ){ SETERR( "null batch" ); return -1; }
-  if( b->spec_fn ) return 0;
+  *mod = NULL; *fn = NULL;
   if( b->lds_bytes > 64*1024 ){ SETERR( "rkfdBatchSpecialize: worlds above 64 KiB of LDS per instance keep the generic kernel" ); return -1; }
-  HIPCHK( hipSetDevice( b->device ), -1 );
-  if( sync_streams( b ) < 0 ) return -1;
   std::vector<char> code;
-  if( spec_compile( b->ipw == 2 ? b->host2.dm : b->dm, code, b->ipw == 2 ? 2 : 1 ) < 0 ) return -1;
-  HIPCHK( hipModuleLoadData( &b->spec_mod, code.data() ), -1 );
-
-  HIPCHK( hipModuleGetFunction( &b->spec_fn, b->spec_mod, "rkfd_step_kernel_spec" ), -1 );
+  if( spec_compile( b->ipw == 2 ? b->host2.dm : b->dm, code, b->ipw == 2 ? 2 : 1, par ) < 0 ) return -1;
+  HIPCHK( hipModuleLoadData( mod, code.data() ), -1 );
+  if( hipModuleGetFunction( fn, *mod, "rkfd_step_kernel_spec" ) != hipSuccess ){
+    (void)hipModuleUnload( *mod ); *mod = NULL; *fn = NULL;
+    SETERR( "rkfdBatchSpecialize: the code object lacks rkfd_step_kernel_spec" ); return -1;
+  }
   if( b->ipw == 2 && wg2_bytes( b ) > 64*1024 ){
     /* (a workgroup of two instances above 64 KiB of LDS needs the opt-in, as the generic kernels get it in rkfdBatchCreate) */
-    const hipError_t e = hipFuncSetAttribute( (const void *)b->spec_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg2_bytes( b ) );
+    const hipError_t e = hipFuncSetAttribute( (const void *)*fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg2_bytes( b ) );
     if( e != hipSuccess ){
-      (void)hipModuleUnload( b->spec_mod ); b->spec_mod = NULL; b->spec_fn = NULL;
+      (void)hipModuleUnload( *mod ); *mod = NULL; *fn = NULL;
       SETERR( "hipFuncSetAttribute(LDS=%zu) failed: %s", wg2_bytes( b ), hipGetErrorString( e ) );
       return -1;
     }
@@ -756,17 +800,28 @@ extern "C" int rkfdBatchSpecialize(rkfdBatch *b)
     /* the compiler behind hipRTC is whichever libamd_comgr the process loaded first; a framework that bundles an older
      * one (PyTorch does) gives a kernel that spills (437 VGPR spills, 3.9 M instead of 14 M steps/s on config 4): refuse it */
     int regs = -1, scratch = -1;
-    hipFuncGetAttribute( &regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, b->spec_fn );
-    hipFuncGetAttribute( &scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, b->spec_fn );
-    if( getenv( "RKFD_SPEC_DEBUG" ) ) fprintf( stderr, "rkfdBatchSpecialize: %d instance(s) per wavefront, %d VGPRs, %d bytes of scratch per lane, %zu bytes of LDS per instance\n", b->ipw == 2 ? 2 : 1, regs, scratch, b->ipw == 2 ? b->host2.lds_bytes : b->lds_bytes );
+    hipFuncGetAttribute( &regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, *fn );
+    hipFuncGetAttribute( &scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, *fn );
+    if( getenv( "RKFD_SPEC_DEBUG" ) ) fprintf( stderr, "rkfdBatchSpecialize: %d instance(s) per wavefront, %s table of per-instance parameters, %d VGPRs, %d bytes of scratch per lane, %zu bytes of LDS per instance\n", b->ipw == 2 ? 2 : 1, par ? "with a" : "no", regs, scratch, b->ipw == 2 ? b->host2.lds_bytes : b->lds_bytes );
     if( scratch > ( b->dm.vol_np > 0 ? 512 : 160 ) ){      /* (the Volume variant is built for two waves per SIMD and spills a few registers on purpose; worlds with two moving
                                                              * contact sides sit at the 168-register limit and spill a handful - tools/spec_resources.py; the wrong compiler: 912 B) */
-      (void)hipModuleUnload( b->spec_mod ); b->spec_mod = NULL; b->spec_fn = NULL;
+      (void)hipModuleUnload( *mod ); *mod = NULL; *fn = NULL;
       SETERR( "rkfdBatchSpecialize: the compiler hipRTC resolved to in this process produced a spilling kernel (%d VGPRs, %d bytes of scratch per lane); "
               "point RKFD_ROCM_LIBDIR at the ROCm libraries this library was built with; the generic kernel stays in use", regs, scratch );
       return -1;
     }
   }
+  return 0;
+}
+extern "C" int rkfdBatchSpecialize(rkfdBatch *b)
+{
+  if( !b ){ SETERR( "null batch" ); return -1; }
+  if( b->spec_fn ) return 0;
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  if( sync_streams( b ) < 0 ) return -1;
+  hipModule_t mod; hipFunction_t fn;
+  if( spec_build( b, b->d_par ? 1 : 0, &mod, &fn ) < 0 ) return -1;
+  b->spec_mod = mod; b->spec_fn = fn; b->spec_par = b->d_par ? 1 : 0;
   return 0;
 }
 
@@ -957,6 +1012,142 @@ extern "C" int rkfdBatchUpdateControlledDev(rkfdBatch *b, int nsteps, const doub
 {
   if( !b || !u_dev || nsteps < 1 ){ SETERR( "rkfdBatchUpdateControlledDev: %s", !b ? "null batch" : !u_dev ? "null schedule" : "nsteps must be >= 1" ); return -1; }
   return launch( b, 0, nsteps, stream, u_dev, false );
+}
+
+/* ---- per-instance physical parameters ----------------------------------------------------------------------- */
+static const double *model_par(const rkfdModel *m, int which)
+{
+  switch( which ){
+  case RKFD_PAR_MASS: return m->mass; case RKFD_PAR_COM: return m->com; case RKFD_PAR_INERTIA: return m->inertia;
+  case RKFD_PAR_STIFF: return m->stiff; case RKFD_PAR_VISC: return m->visc; case RKFD_PAR_COULOMB: return m->coulomb; case RKFD_PAR_SFRIC: return m->sfric;
+  case RKFD_PAR_CI_SF: return m->ci_sf; case RKFD_PAR_CI_KF: return m->ci_kf; case RKFD_PAR_CI_K: return m->ci_k;
+  case RKFD_PAR_CI_L: return m->ci_l; case RKFD_PAR_CI_E: return m->ci_e; case RKFD_PAR_CI_V: return m->ci_v;
+  }
+  return NULL;
+}
+static const char *const g_par_name[RKFD_PAR_COUNT] = { "mass", "com", "inertia", "stiff", "visc", "coulomb", "sfric", "ci_sf", "ci_kf", "ci_k", "ci_l", "ci_e", "ci_v" };
+extern "C" int rkfdBatchParamWidth(const rkfdBatch *b, int which)
+{
+  if( !b || which < 0 || which >= RKFD_PAR_COUNT ) return -1;
+  if( which >= RKFD_PAR_CI_SF ) return b->model_for_w2->nci;
+  return b->nlink*( which == RKFD_PAR_COM ? 3 : ( which == RKFD_PAR_INERTIA ? 9 : 1 ) );
+}
+extern "C" int rkfdBatchHasParams(const rkfdBatch *b){ return b && b->d_par ? 1 : 0; }
+/* what rkfdBatchSetParam refuses (nothing has been changed when it does) */
+static int par_check(const rkfdBatch *b, int which, const double *values)
+{
+  if( !b ){ SETERR( "rkfdBatchSetParam: null batch" ); return -1; }
+  if( which < 0 || which >= RKFD_PAR_COUNT ){ SETERR( "rkfdBatchSetParam: unknown parameter key %d (0 .. %d)", which, RKFD_PAR_COUNT-1 ); return -1; }
+  if( !values ) return 0;
+  const int w = rkfdBatchParamWidth( b, which );
+  for( int i=0; i<b->batch; i++ )
+    for( int j=0; j<w; j++ ){
+      const double x = values[(size_t)i*w+j];
+      if( !( x - x == 0.0 ) ){ SETERR( "rkfdBatchSetParam: %s of instance %d, entry %d is not finite", g_par_name[which], i, j ); return -1; }
+      if( which == RKFD_PAR_MASS && x < 0 ){ SETERR( "rkfdBatchSetParam: negative mass %g for link %d of instance %d", x, j, i ); return -1; }
+      if( which == RKFD_PAR_MASS && x == 0 && b->model_for_w2->mass[j] > 0 ){
+        SETERR( "rkfdBatchSetParam: mass 0 for link %d of instance %d, whose mass is positive in the model (a massless link is another world)", j, i );
+        return -1;
+      }
+    }
+  return 0;
+}
+/* what the table's launches may still be reading: the internal streams and the caller's stream of the last launch (launches a
+ * caller made on OTHER streams of its own must be joined by the caller first: rkfdBatchJoin / rkfdBatchStatus) */
+static int par_quiesce(rkfdBatch *b)
+{
+  if( sync_streams( b ) < 0 ) return -1;
+  HIPCHK( hipStreamSynchronize( b->last_stream ), -1 );
+  return 0;
+}
+/* the device table from a host copy h[key][batch][width]: every instance's row through rkfd_devmodel_par_row */
+static int par_upload(rkfdBatch *b, double *const *h, double *d, size_t stride)
+{
+  std::vector<double> tab( (size_t)b->batch*stride + 1 );
+  for( int i=0; i<b->batch; i++ ){
+    const double *par[RKFD_PAR_COUNT];
+    for( int k=0; k<RKFD_PAR_COUNT; k++ ) par[k] = h[k] + (size_t)i*rkfdBatchParamWidth( b, k );
+    rkfd_devmodel_par_row( &b->host, par, &tab[(size_t)i*stride] );
+  }
+  HIPCHK( hipMemcpy( d, tab.data(), sizeof(double)*(size_t)b->batch*stride, hipMemcpyHostToDevice ), -1 );
+  return 0;
+}
+/* Everything that can fail - the allocations, the world-specific kernel for batches with a table when the batch runs a
+ * world-specific kernel (from the store `make spec` fills for the configurations of BASELINE.json, else a run-time compile of a few
+ * seconds, kept in the store), the upload - happens BEFORE the batch is touched: a call that returns -1 has changed nothing. */
+extern "C" int rkfdBatchSetParam(rkfdBatch *b, int which, const double *values)
+{
+  if( par_check( b, which, values ) < 0 ) return -1;
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  if( par_quiesce( b ) < 0 ) return -1;
+  const int w = rkfdBatchParamWidth( b, which );
+  if( b->d_par ){
+    /* a table exists: the new values of this key into a copy of its array, the table rebuilt in place only once nothing can fail
+     * but the copy to the device (which leaves the host copy as it was, and the next successful Set rewrites the whole table) */
+    const size_t n = (size_t)b->batch*w;
+    double *nk = (double *)malloc( sizeof(double)*( n + 1 ) );
+    if( !nk ){ SETERR( "rkfdBatchSetParam: out of memory" ); return -1; }
+    if( values ) memcpy( nk, values, sizeof(double)*n );
+    else for( int i=0; i<b->batch; i++ ) memcpy( nk + (size_t)i*w, model_par( b->model_for_w2, which ), sizeof(double)*w );
+    double *h[RKFD_PAR_COUNT];
+    for( int k=0; k<RKFD_PAR_COUNT; k++ ) h[k] = k == which ? nk : b->h_par[k];
+    if( par_upload( b, h, b->d_par, (size_t)b->par_stride ) < 0 ){ free( nk ); return -1; }
+    free( b->h_par[which] ); b->h_par[which] = nk;
+    return 0;
+  }
+  if( !values ) return 0;      /* no table: every key is the model's already */
+  const size_t stride = rkfd_devmodel_par_stride( &b->host );
+  if( (double)stride*(double)b->batch >= 2147483647.0 ){ SETERR( "rkfdBatchSetParam: the table of %d instances x %zu doubles is beyond the 2^31 doubles an instance's row offset can address", b->batch, stride ); return -1; }
+  double *h[RKFD_PAR_COUNT];
+  double *d = NULL;
+  hipModule_t mod = NULL; hipFunction_t fn = NULL;
+  int ok = 1;
+  for( int k=0; k<RKFD_PAR_COUNT; k++ ) h[k] = NULL;
+  for( int k=0; k<RKFD_PAR_COUNT && ok; k++ ){
+    const int wk = rkfdBatchParamWidth( b, k );
+    h[k] = (double *)malloc( sizeof(double)*( (size_t)b->batch*wk + 1 ) );
+    if( !h[k] ){ SETERR( "rkfdBatchSetParam: out of memory" ); ok = 0; break; }
+    if( k == which ) memcpy( h[k], values, sizeof(double)*(size_t)b->batch*wk );
+    else for( int i=0; i<b->batch; i++ ) memcpy( h[k] + (size_t)i*wk, model_par( b->model_for_w2, k ), sizeof(double)*wk );
+  }
+  if( ok && hipMalloc( (void **)&d, sizeof(double)*( stride*(size_t)b->batch + 1 ) ) != hipSuccess ){
+    SETERR( "rkfdBatchSetParam: cannot allocate the table on the device (%zu bytes)", sizeof(double)*stride*(size_t)b->batch ); d = NULL; ok = 0;
+  }
+  if( ok && par_upload( b, h, d, stride ) < 0 ) ok = 0;
+  /* a batch that runs a world-specific kernel gets the one built for batches with a table */
+  if( ok && b->spec_fn && spec_build( b, 1, &mod, &fn ) < 0 ) ok = 0;
+  if( !ok ){
+    for( int k=0; k<RKFD_PAR_COUNT; k++ ) free( h[k] );
+    (void)hipFree( d );
+    return -1;
+  }
+  for( int k=0; k<RKFD_PAR_COUNT; k++ ) b->h_par[k] = h[k];
+  b->d_par = d; b->par_stride = (int)stride;
+  if( fn ){ (void)hipModuleUnload( b->spec_mod ); b->spec_mod = mod; b->spec_fn = fn; b->spec_par = 1; }
+  return 0;
+}
+extern "C" int rkfdBatchGetParam(rkfdBatch *b, int which, double *values)
+{
+  if( !b || !values ){ SETERR( "rkfdBatchGetParam: null argument" ); return -1; }
+  const int w = rkfdBatchParamWidth( b, which );
+  if( w < 0 ){ SETERR( "rkfdBatchGetParam: unknown parameter key %d (0 .. %d)", which, RKFD_PAR_COUNT-1 ); return -1; }
+  if( b->d_par ) memcpy( values, b->h_par[which], sizeof(double)*(size_t)b->batch*w );
+  else for( int i=0; i<b->batch; i++ ) memcpy( values + (size_t)i*w, model_par( b->model_for_w2, which ), sizeof(double)*w );
+  return 0;
+}
+extern "C" int rkfdBatchClearParams(rkfdBatch *b)
+{
+  if( !b ){ SETERR( "rkfdBatchClearParams: null batch" ); return -1; }
+  if( !b->d_par ) return 0;
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  if( par_quiesce( b ) < 0 ) return -1;
+  /* (the kernel for batches without a table first: when it cannot be had, the table stays) */
+  hipModule_t mod = NULL; hipFunction_t fn = NULL;
+  if( b->spec_fn && spec_build( b, 0, &mod, &fn ) < 0 ) return -1;
+  if( fn ){ (void)hipModuleUnload( b->spec_mod ); b->spec_mod = mod; b->spec_fn = fn; b->spec_par = 0; }
+  (void)hipFree( b->d_par ); b->d_par = NULL; b->par_stride = 0;
+  for( int k=0; k<RKFD_PAR_COUNT; k++ ){ free( b->h_par[k] ); b->h_par[k] = NULL; }
+  return 0;
 }
 
 /* diagnostic: nsteps x rkFDUpdate with in-kernel phase stamps; out[batch][8] shader-clock cycles of

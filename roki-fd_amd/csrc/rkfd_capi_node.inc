@@ -238,6 +238,26 @@ extern "C" int rkfdNodeSetState(rkfdNode *n, const double *dis, const double *ve
     if( rkfdBatchSetState( n->b[k], dis + (size_t)n->lo[k]*n->ndof, vel + (size_t)n->lo[k]*n->ndof ) < 0 ) return -1;
   return 0;
 }
+/* per-instance parameters over all instances: every shard is checked before any is changed */
+extern "C" int rkfdNodeSetParam(rkfdNode *n, int which, const double *values)
+{
+  if( !n ){ SETERR( "rkfdNodeSetParam: null node" ); return -1; }
+  for( int k=0; k<n->ndev; k++ ){
+    const int w = rkfdBatchParamWidth( n->b[k], which );
+    if( par_check( n->b[k], which, values && w > 0 ? values + (size_t)n->lo[k]*w : values ) < 0 ) return -1;
+  }
+  for( int k=0; k<n->ndev; k++ ){
+    const int w = rkfdBatchParamWidth( n->b[k], which );
+    if( rkfdBatchSetParam( n->b[k], which, values ? values + (size_t)n->lo[k]*w : NULL ) < 0 ) return -1;
+  }
+  return 0;
+}
+extern "C" int rkfdNodeClearParams(rkfdNode *n)
+{
+  if( !n ){ SETERR( "rkfdNodeClearParams: null node" ); return -1; }
+  for( int k=0; k<n->ndev; k++ ) if( rkfdBatchClearParams( n->b[k] ) < 0 ) return -1;
+  return 0;
+}
 extern "C" int rkfdNodeSetMotorInput(rkfdNode *n, const double *input)
 {
   if( !n || !input ){ SETERR( "rkfdNodeSetMotorInput: null argument" ); return -1; }

@@ -29,6 +29,70 @@ struct Blob {
 };
 }
 
+
+/* Composite rigid bodies: mass, centre of mass and inertia of every device link from those of the model links merged into it
+ * (parts part_idx[part_off[r] .. part_off[r+1]) of device link r, Trep[12 i] the frame of model link i in its device link).  A function
+ * of the inertial parameters alone: the builder runs it on the model's, rkfd_devmodel_par_row on an instance's own
+ * (rkfdBatchSetParam) - the same code, so a row of the table holds the bits a model with those parameters would have been built to. */
+static void merge_inertia(int NL, const int *part_off, const int *part_idx, const double *Trep,
+                          const double *mass, const double *com_m, const double *inertia, double *R_mass, double *R_com, double *R_inertia)
+{
+  for( int r=0; r<NL; r++ ){
+    double M = 0, mc[3] = {0,0,0};
+    std::vector<double> cs;                         /* part centres of mass in the device link frame */
+    for( int q=part_off[r]; q<part_off[r+1]; q++ ){
+      const int i = part_idx[q];
+      const double *T = &Trep[12*i], *c = &com_m[3*i];
+      double cc[3];
+      for( int a=0; a<3; a++ ) cc[a] = T[9+a] + T[3*a]*c[0] + T[3*a+1]*c[1] + T[3*a+2]*c[2];
+      cs.insert( cs.end(), cc, cc+3 );
+      M += mass[i];
+      for( int a=0; a<3; a++ ) mc[a] += mass[i]*cc[a];
+    }
+    double com[3] = {0,0,0};
+    if( M > 0 ) for( int a=0; a<3; a++ ) com[a] = mc[a]/M;
+    else if( !cs.empty() ) for( int a=0; a<3; a++ ) com[a] = cs[a];
+    double I[9] = {0,0,0,0,0,0,0,0,0};
+    for( int q=part_off[r]; q<part_off[r+1]; q++ ){
+      const int i = part_idx[q], k = q - part_off[r];
+      const double *T = &Trep[12*i], *Ii = &inertia[9*i];
+      double RI[9], RIRt[9];
+      for( int a=0; a<3; a++ ) for( int b=0; b<3; b++ ) RI[3*a+b] = T[3*a]*Ii[b] + T[3*a+1]*Ii[3+b] + T[3*a+2]*Ii[6+b];
+      for( int a=0; a<3; a++ ) for( int b=0; b<3; b++ ) RIRt[3*a+b] = RI[3*a]*T[3*b] + RI[3*a+1]*T[3*b+1] + RI[3*a+2]*T[3*b+2];
+      const double d[3] = { cs[3*k]-com[0], cs[3*k+1]-com[1], cs[3*k+2]-com[2] };
+      const double d2 = d[0]*d[0] + d[1]*d[1] + d[2]*d[2];
+      for( int a=0; a<3; a++ ) for( int b=0; b<3; b++ )
+        I[3*a+b] += RIRt[3*a+b] + mass[i]*( ( a == b ? d2 : 0.0 ) - d[a]*d[b] );
+    }
+    R_mass[r] = M;
+    for( int a=0; a<3; a++ ) R_com[3*r+a] = com[a];
+    for( int a=0; a<9; a++ ) R_inertia[9*r+a] = I[a];
+  }
+}
+
+/* one row of the table of per-instance parameters, in device space: mass | com | inertia | stiff | visc | coulomb | sfric of the
+ * device links, then ci_sf .. ci_v - from the thirteen model-space arrays of one instance, in the order of the RKFD_PAR_* keys */
+extern "C" size_t rkfd_devmodel_par_stride(const rkfdDevModelHost *h){ return (size_t)17*h->dm.nlink + (size_t)6*h->dm.nci; }
+extern "C" void rkfd_devmodel_par_row(const rkfdDevModelHost *h, const double *const *par, double *row)
+{
+  const int NL = h->dm.nlink, nci = h->dm.nci;
+  merge_inertia( NL, h->part_off, h->part_idx, h->part_frame, par[0], par[1], par[2], row, row + NL, row + 4*NL );
+  for( int k=0; k<4; k++ )
+    for( int r=0; r<NL; r++ ) row[( 13+k )*NL + r] = par[3+k][h->dm.orig[r]];
+  for( int k=0; k<6; k++ )
+    for( int c=0; c<nci; c++ ) row[17*NL + k*nci + c] = par[7+k][c];
+}
+/* the device model a launch passes when a table exists: the pointers to those parameters point at its first row */
+extern "C" void rkfd_devmodel_par_bind(rkfdDevModel *d, const double *table)
+{
+  const double *p = table;
+  const int NL = d->nlink, nci = d->nci;
+  d->mass = p; d->com = p + NL; d->inertia = p + 4*NL;
+  d->stiff = p + 13*NL; d->visc = p + 14*NL; d->coulomb = p + 15*NL; d->sfric = p + 16*NL;
+  p += 17*NL;
+  d->ci_sf = p; d->ci_kf = p + nci; d->ci_k = p + 2*nci; d->ci_l = p + 3*nci; d->ci_e = p + 4*nci; d->ci_v = p + 5*nci;
+}
+
 extern "C" int rkfd_devmodel_build(const rkfdModel *m, int max_rigid, rkfdDevModelHost *out, char *err, int errlen)
 {
   return rkfd_devmodel_build_w( m, max_rigid, 8, out, err, errlen );
@@ -136,37 +200,12 @@ extern "C" int rkfd_devmodel_build_w(const rkfdModel *m, int max_rigid, const in
   if( NG != 8 && NG != 4 ) FAIL( "ngroup must be 8 or 4" );
   if( NL > RKFD_MAX_LINK ) FAIL( "nlink %d (after merging fixed links) exceeds the per-wave limit %d", NL, RKFD_MAX_LINK );
   std::vector<double> R_mass( NL, 0.0 ), R_com( (size_t)3*NL, 0.0 ), R_inertia( (size_t)9*NL, 0.0 );
+  std::vector<int> part_off( NL+1, 0 ), part_idx;
   for( int r=0; r<NL; r++ ){
-    double M = 0, mc[3] = {0,0,0};
-    std::vector<double> cs;                         /* part centres of mass in the device link frame */
-    for( size_t q=0; q<accs[r].parts.size(); q++ ){
-      const int i = accs[r].parts[q];
-      const double *T = &Trep[12*i], *c = &m->com[3*i];
-      double cc[3];
-      for( int a=0; a<3; a++ ) cc[a] = T[9+a] + T[3*a]*c[0] + T[3*a+1]*c[1] + T[3*a+2]*c[2];
-      cs.insert( cs.end(), cc, cc+3 );
-      M += m->mass[i];
-      for( int a=0; a<3; a++ ) mc[a] += m->mass[i]*cc[a];
-    }
-    double com[3] = {0,0,0};
-    if( M > 0 ) for( int a=0; a<3; a++ ) com[a] = mc[a]/M;
-    else if( !cs.empty() ) for( int a=0; a<3; a++ ) com[a] = cs[a];
-    double I[9] = {0,0,0,0,0,0,0,0,0};
-    for( size_t q=0; q<accs[r].parts.size(); q++ ){
-      const int i = accs[r].parts[q];
-      const double *T = &Trep[12*i], *Ii = &m->inertia[9*i];
-      double RI[9], RIRt[9];
-      for( int a=0; a<3; a++ ) for( int b=0; b<3; b++ ) RI[3*a+b] = T[3*a]*Ii[b] + T[3*a+1]*Ii[3+b] + T[3*a+2]*Ii[6+b];
-      for( int a=0; a<3; a++ ) for( int b=0; b<3; b++ ) RIRt[3*a+b] = RI[3*a]*T[3*b] + RI[3*a+1]*T[3*b+1] + RI[3*a+2]*T[3*b+2];
-      const double d[3] = { cs[3*q]-com[0], cs[3*q+1]-com[1], cs[3*q+2]-com[2] };
-      const double d2 = d[0]*d[0] + d[1]*d[1] + d[2]*d[2];
-      for( int a=0; a<3; a++ ) for( int b=0; b<3; b++ )
-        I[3*a+b] += RIRt[3*a+b] + m->mass[i]*( ( a == b ? d2 : 0.0 ) - d[a]*d[b] );
-    }
-    R_mass[r] = M;
-    for( int a=0; a<3; a++ ) R_com[3*r+a] = com[a];
-    for( int a=0; a<9; a++ ) R_inertia[9*r+a] = I[a];
+    part_idx.insert( part_idx.end(), accs[r].parts.begin(), accs[r].parts.end() );
+    part_off[r+1] = (int)part_idx.size();
   }
+  merge_inertia( NL, part_off.data(), part_idx.data(), Trep.data(), m->mass, m->com, m->inertia, R_mass.data(), R_com.data(), R_inertia.data() );
   /* 1-DoF joint parameters of the surviving links */
   std::vector<double> R_stiff( NL ), R_visc( NL ), R_coulomb( NL ), R_sfric( NL ), R_mot_k( NL ), R_mot_admit( NL ),
                       R_mot_vmax( NL ), R_mot_vmin( NL ), R_mot_gear( NL ), R_mot_inertia( NL );
@@ -728,6 +767,14 @@ extern "C" int rkfd_devmodel_build_w(const rkfdModel *m, int max_rigid, const in
     if( !rf ) FAIL( "out of memory" );
     memcpy( rf, refT.data(), sizeof(double)*refT.size() );
     out->ref_frame = rf; out->ncand = NC;
+    /* host-only: which model links make up a device link and where they sit in it (rkfd_devmodel_par_row) */
+    out->part_off = (int *)malloc( sizeof(int)*( NL+1 ) );
+    out->part_idx = (int *)malloc( sizeof(int)*( part_idx.size() + 1 ) );
+    out->part_frame = (double *)malloc( sizeof(double)*Trep.size() );
+    if( !out->part_off || !out->part_idx || !out->part_frame ) FAIL( "out of memory" );
+    memcpy( out->part_off, part_off.data(), sizeof(int)*( NL+1 ) );
+    memcpy( out->part_idx, part_idx.data(), sizeof(int)*part_idx.size() );
+    memcpy( out->part_frame, Trep.data(), sizeof(double)*Trep.size() );
   }
   /* LDS bytes one instance needs (must match rkfd_lds_carve in rkfd_device.h).  Two passes: with the contact matrix
    * as full rows, and - PGS worlds only - as a packed lower triangle, which is taken when it lets one more instance
@@ -788,7 +835,10 @@ extern "C" int rkfd_devmodel_build_w(const rkfdModel *m, int max_rigid, const in
 
 extern "C" void rkfd_devmodel_free(rkfdDevModelHost *h)
 {
-  if( h ){ free( h->blob ); h->blob = NULL; free( (void *)h->ref_frame ); h->ref_frame = NULL; }
+  if( h ){
+    free( h->blob ); h->blob = NULL; free( (void *)h->ref_frame ); h->ref_frame = NULL;
+    free( h->part_off ); h->part_off = NULL; free( h->part_idx ); h->part_idx = NULL; free( h->part_frame ); h->part_frame = NULL;
+  }
 }
 
 extern "C" void rkfd_devmodel_rebase(rkfdDevModel *dm, const void *from, const void *to)

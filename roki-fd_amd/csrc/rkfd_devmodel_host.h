@@ -21,6 +21,10 @@ typedef struct {
    * other model link in its device link (inside blob). */
   const double *ref_frame;
   int ncand;
+  /* the merge of rigidly attached links, kept for rkfd_devmodel_par_row: device link r is made of the model links
+   * part_idx[part_off[r] .. part_off[r+1]), and part_frame[12*i] is the frame of model link i in its device link */
+  int *part_off, *part_idx;
+  double *part_frame;
 } rkfdDevModelHost;
 
 /* anchors between the model link's frame (boundary) and the device link's frame (device state), in place:
@@ -35,6 +39,12 @@ int  rkfd_devmodel_build(const rkfdModel *m, int max_rigid, rkfdDevModelHost *ou
  * slots - and use neither the Vert QP nor the Volume plugin, else the call fails with a message) */
 int  rkfd_devmodel_build_w(const rkfdModel *m, int max_rigid, int ngroup, rkfdDevModelHost *out, char *err, int errlen);
 void rkfd_devmodel_free(rkfdDevModelHost *h);
+/* per-instance physical parameters (rkfdBatchSetParam): doubles of one row of the device table, and the row of one instance from its
+ * thirteen model-space arrays par[RKFD_PAR_MASS .. RKFD_PAR_CI_V] - the composite bodies through the code the builder runs */
+size_t rkfd_devmodel_par_stride(const rkfdDevModelHost *h);
+void rkfd_devmodel_par_row(const rkfdDevModelHost *h, const double *const *par, double *row);
+/* point dm's mass .. sfric and ci_sf .. ci_v at the first row of a table of such rows (device or host addresses, as dm's own) */
+void rkfd_devmodel_par_bind(rkfdDevModel *dm, const double *table);
 /* shift every pointer of dm from the blob at `from` to its copy at `to` */
 void rkfd_devmodel_rebase(rkfdDevModel *dm, const void *from, const void *to);
 

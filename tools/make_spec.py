@@ -17,16 +17,18 @@ for nm in names:
     sc = R.scenarios.CONFIGS[nm](batch=1)
     if L.rkfdLdsBytesFor(sc["world"].model, sc["max_rigid"]) > 64 * 1024:
         print("%-16s keeps the generic kernel (more than 64 KiB of LDS per instance)" % nm); continue
-    t0 = time.time()
-    n = L.rkfdSpecializeCompile(sc["world"].model, sc["max_rigid"])
-    if n <= 0:
-        print("%-16s FAILED: %s" % (nm, L.rkfdHipLastError().decode())); sys.exit(1)
-    print("%-16s %6d bytes  %s  (%.1f s)" % (nm, n, "already in the store" if L.rkfdSpecializeLastFromStore() else "compiled", time.time() - t0), flush=True)
-    # the kernel with two instances per wavefront, for the worlds eligible for it (rkfdBatchTuneInstancesPerWave picks by measurement)
-    t0 = time.time()
-    n = L.rkfdSpecializeCompileW(sc["world"].model, sc["max_rigid"], 2)
-    if n > 0:
-        print("%-16s %6d bytes  %s  (%.1f s)  [two instances per wavefront]" % (nm, n, "already in the store" if L.rkfdSpecializeLastFromStore() else "compiled", time.time() - t0), flush=True)
+    # four kernels per world: one / two instances per wavefront (the worlds eligible for two; rkfdBatchTuneInstancesPerWave picks by
+    # measurement), each without and with a table of per-instance parameters (rkfdBatchSetParam)
+    for ipw in (1, 2):
+        for par in (0, 1):
+            t0 = time.time()
+            n = L.rkfdSpecializeCompileP(sc["world"].model, sc["max_rigid"], ipw, par)
+            if n <= 0:
+                if ipw == 1:
+                    print("%-16s FAILED: %s" % (nm, L.rkfdHipLastError().decode())); sys.exit(1)
+                continue
+            print("%-16s %6d bytes  %s  (%.1f s)%s%s" % (nm, n, "already in the store" if L.rkfdSpecializeLastFromStore() else "compiled", time.time() - t0,
+                                                       "  [two instances per wavefront]" if ipw == 2 else "", "  [per-instance parameters]" if par else ""), flush=True)
 
 if not sys.argv[1:]:
     import glob, shutil
@@ -36,7 +38,7 @@ if not sys.argv[1:]:
     # library for its keys - so a full run compiles into a fresh directory when the store holds more files than it just produced
     have = glob.glob(os.path.join(spec, "rkfd_spec_*.co"))
     fresh = [f for f in have if os.path.getmtime(f) >= t_start - 1]
-    if len(have) > 2 * len(names) + 8 and not os.environ.get("RKFD_SPEC_PRUNED"):
+    if len(have) > 4 * len(names) + 8 and not os.environ.get("RKFD_SPEC_PRUNED"):
         tmp = spec + ".new"
         shutil.rmtree(tmp, ignore_errors=True); os.makedirs(tmp)
         env = dict(os.environ, RKFD_SPEC_DIR=tmp, RKFD_SPEC_PRUNED="1")
