@@ -218,6 +218,38 @@ int rkfdBatchResidency(const rkfdBatch *b);
 /* the same figure computed on the host for a model and contact capacity (no GPU needed) */
 int rkfdLdsBytesFor(const rkfdModel *m, int max_rigid);
 
+/* ---- task-space read-out: link poses, link velocities and chain centres of mass, computed ON THE DEVICE from the live state ----
+ * What an MPC / RL cost is made of (base height and tilt, foot and hand positions, the centre of mass, a link's velocity) without
+ * copying the joint state to the host and re-doing the forward kinematics there.  One kernel launch (rkfd_links_kernel, a kernel
+ * of its own: the step kernels are untouched) computes, for every instance,
+ *   R      [batch][nlink][3][3]  orientation of every MODEL link, row-major, link -> world
+ *   p      [batch][nlink][3]     position of its origin, world (absolute)
+ *   v      [batch][nlink][6]     (linear, angular) velocity of the link origin, in the link's OWN frame (DEVIATIONS.md item 1)
+ *   com    [batch][nchain][3]    centre of mass of every chain, world:  sum m_i ( p_i + R_i c_i ) / sum m_i
+ *   comvel [batch][nchain][3]    its velocity, world:                   sum m_i R_i ( v_i + w_i x c_i ) / sum m_i
+ * (a chain without mass reports zeros; a batch with a table of per-instance parameters uses the instance's masses and centres of
+ * mass).  Links are the model's links, as everywhere at this boundary: rigidly attached links the device merges and the three
+ * device links of a spherical joint are resolved here.  A breakable float joint sits where its six coordinates put it, broken
+ * or not.  Link accelerations, contact point positions, a subset of links and per-step values inside a fused launch are not given
+ * (DEVIATIONS.md): read per step, or at the end of a rollout.
+ * A batch that never calls these allocates nothing and launches nothing; snapshot / restore do not save the results (derived data). */
+enum { RKFD_LINKS_POSE = 1, RKFD_LINKS_VEL = 2, RKFD_LINKS_COM = 4 };
+int rkfdBatchLinkNum(const rkfdBatch *b);            /* model links */
+int rkfdBatchChainNum(const rkfdBatch *b);
+/* computes the selected quantities from the live state, in stream order after everything the batch has launched (joins the
+ * internal split streams onto `stream` first, as rkfdBatchJoin does); asynchronous; changes no state */
+int rkfdBatchUpdateLinks(rkfdBatch *b, int flags, void *stream);
+/* host copies of the last rkfdBatchUpdateLinks (waits for it); any pointer may be NULL; -1 with a message when a requested
+ * quantity was not part of the last read-out or none was made */
+int rkfdBatchGetLinks(rkfdBatch *b, double *R, double *p, double *v, double *com, double *comvel);
+/* device pointers to the same buffers (owned by the batch, allocated at the first read-out that needs them, stable afterwards;
+ * NULL before) */
+const double *rkfdBatchDevLinkAtt(rkfdBatch *b);
+const double *rkfdBatchDevLinkPos(rkfdBatch *b);
+const double *rkfdBatchDevLinkVel(rkfdBatch *b);
+const double *rkfdBatchDevCom(rkfdBatch *b);
+const double *rkfdBatchDevComVel(rkfdBatch *b);
+
 /* ---- the node level: all the GPUs of one node from ONE process, host code in C -------------------------------------
  * SURVEY 8e / north star: "independent MPC-style rollouts shard embarrassingly across the 8 GPUs of one node with an
  * RCCL-over-xGMI gather of final states only".  The instances of a batch are independent (one rkFD never references another),
@@ -259,6 +291,9 @@ int rkfdNodeUpdateControlled(rkfdNode *n, int nsteps, const double *u);
  * rkfdNodeSetState (NULL: the key back to the model's value everywhere).  Nothing is changed on any device when one refuses. */
 int rkfdNodeSetParam(rkfdNode *n, int which, const double *values);
 int rkfdNodeClearParams(rkfdNode *n);
+/* rkfdBatchUpdateLinks( flags ) on every device's own thread and stream, then host arrays over ALL instances in instance order
+ * (shapes as rkfdBatchGetLinks with batch = total; pointers of quantities `flags` does not select must be NULL) */
+int rkfdNodeGetLinks(rkfdNode *n, int flags, double *R, double *p, double *v, double *com, double *comvel);
 /* one ncclAllGather of the final {dis, vel}: afterwards every device holds all `total` final states (rkfdNodeGatherDev: on
  * device k, [ndev][mx][2 ndof] doubles - block j = shard j's instances, dis | vel per instance, padded to the largest shard mx),
  * and dis / vel ([total][ndof], either may be NULL) receive them on the host in instance order */

@@ -180,8 +180,18 @@ void rkCDPairChainUnreg(rkFDCD *cd, rkChain *chain);
 /* rkFDFK / rkFDUpdateRate / rkFDUpdateFKRate (reference src/rkfd_sim.c:344-384): in the reference they push a packed
  * state into the chains' link frames / rates on the host.  Link frames and rates live on the device here and are
  * recomputed from the packed state by every evaluation, so these calls set the packed state the next
- * rkFDUpdateInit / rkFDUpdate starts from (dis; vel and acc) - there is no host-side kinematics to refresh. */
+ * rkFDUpdateInit / rkFDUpdate starts from (dis; vel and acc).  The frames themselves are read off the device with
+ * rkfdChainLinkWldPos / rkfdChainLinkWldAtt / rkfdChainWldCOM below (one read-out kernel per step that asks, none otherwise). */
 void rkFDFK(rkFD *fd, zVec dis);
+/* What RoKi's rkChainLinkWldPos / rkChainLinkWldAtt / rkChainWldCOM give after rkFDUpdate (those macros return pointers into
+ * structures this build does not have, hence the rkfd prefix and the output arguments): world position and orientation
+ * (row-major, link -> world) of link number `link` of a registered chain and the chain's centre of mass, at the state the last
+ * rkFDUpdateInit / rkFDUpdate left on the device.  The first such call after an update runs one read-out on the device
+ * (rkfdBatchUpdateLinks) and copies it over; later calls reuse it.  Without a device batch, or for a link the chain does not
+ * have, they give zeros / the identity and say so on stderr. */
+void rkfdChainLinkWldPos(rkChain *c, int link, double p[3]);
+void rkfdChainLinkWldAtt(rkChain *c, int link, double R[9]);
+void rkfdChainWldCOM(rkChain *c, double com[3]);
 void rkFDUpdateRate(rkFD *fd, zVec vel, zVec acc);
 void rkFDUpdateFKRate(rkFD *fd);
 /* rkChainFPrintZTK of every registered chain at its current joint displacements (reference src/rkfd_sim.c:587-593) */

@@ -8,6 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "librkfd_amd.so")
 
 JOINT_FIXED, JOINT_REVOL, JOINT_PRISM, JOINT_FLOAT = 0, 1, 2, 3
+JOINT_SPHER, JOINT_BRFLOAT = 4, 5
 SOLVER_VERT, SOLVER_MLCP, SOLVER_VOLUME = 0, 1, 2
 CONTACT_RIGID, CONTACT_ELASTIC = 0, 1
 SF, KF = 0, 1
@@ -116,6 +117,12 @@ def lib():
     for f in ("rkfdBatchDevDis", "rkfdBatchDevVel", "rkfdBatchDevAcc"):
         getattr(L, f).argtypes = [vp]
         getattr(L, f).restype = vp
+    L.rkfdBatchLinkNum.argtypes = [vp]; L.rkfdBatchChainNum.argtypes = [vp]
+    L.rkfdBatchUpdateLinks.argtypes = [vp, C.c_int, vp]; L.rkfdBatchGetLinks.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.rkfdNodeGetLinks.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    for f in ("rkfdBatchDevLinkAtt", "rkfdBatchDevLinkPos", "rkfdBatchDevLinkVel", "rkfdBatchDevCom", "rkfdBatchDevComVel"):
+        getattr(L, f).argtypes = [vp]
+        getattr(L, f).restype = vp
     L.rkfdNodeCreate.argtypes = [C.POINTER(RkfdModel), C.c_int, C.c_int, C.c_int, vp]; L.rkfdNodeCreate.restype = vp
     L.rkfdNodeDestroy.argtypes = [vp]
     for f in ("rkfdNodeDevices", "rkfdNodeSize", "rkfdNodeSpecialize", "rkfdNodeUpdateInit", "rkfdNodeSnapshot", "rkfdNodeRestore", "rkfdNodeStatus"):
@@ -206,6 +213,18 @@ class World:
         return buf[:n].copy()
 
 
+# task-space read-out (include/rkfd_hip.h: RKFD_LINKS_*): what update_links computes and get_links returns
+LINKS_POSE, LINKS_VEL, LINKS_COM = 1, 2, 4
+LINKS_ALL = LINKS_POSE | LINKS_VEL | LINKS_COM
+_LINKS_KEYS = (("R", LINKS_POSE), ("p", LINKS_POSE), ("v", LINKS_VEL), ("com", LINKS_COM), ("comvel", LINKS_COM))
+
+
+def _links_arrays(n, nl, nc, flags):
+    """host arrays of a read-out over n instances: {name: array} of the quantities `flags` selects"""
+    shapes = {"R": (n, nl, 3, 3), "p": (n, nl, 3), "v": (n, nl, 6), "com": (n, nc, 3), "comvel": (n, nc, 3)}
+    return {k: np.empty(shapes[k]) for k, f in _LINKS_KEYS if flags & f}
+
+
 # per-instance physical parameters (include/rkfd_hip.h: RKFD_PAR_*): the key of a name is its place here
 PARAM_NAMES = ("mass", "com", "inertia", "stiff", "visc", "coulomb", "sfric", "ci_sf", "ci_kf", "ci_k", "ci_l", "ci_e", "ci_v")
 
@@ -229,6 +248,8 @@ class Batch:
         self.world = world
         m = world.model.contents
         self.B, self.ndof, self.nlink, self.ncand = batch, m.ndof, m.nlink, m.ncand
+        self.nchain = m.nchain
+        self._links_flags = 0          # what the last update_links() computed
         self.device = device
         self._ctrl_keep = []           # device schedules of update_controlled() the launches issued since the last join / sync read
         self._b = self._L.rkfdBatchCreate(world.model, batch, device, max_rigid)
@@ -444,18 +465,50 @@ class Batch:
         """instances per compute unit the HIP runtime can keep resident (registers + LDS)"""
         return self._L.rkfdBatchResidency(self._b)
 
-    def dev_tensors(self):
+    def update_links(self, flags=LINKS_ALL, stream=None):
+        """task-space read-out ON THE DEVICE from the live state: poses (LINKS_POSE) and velocities (LINKS_VEL) of every model
+        link, centre of mass and its velocity of every chain (LINKS_COM).  One kernel launch in stream order after everything the
+        batch has launched (no host wait, no state changed); get_links() / links_tensors() / dev_tensors(links=True) hand the results out."""
+        self._chk(self._L.rkfdBatchUpdateLinks(self._b, int(flags), stream))
+        self._links_flags = int(flags)
+
+    def get_links(self):
+        """host copies of the last update_links(): a dict with (of what its flags selected) R [B, nl, 3, 3] (row-major, link ->
+        world), p [B, nl, 3] (world), v [B, nl, 6] ((linear, angular) of the link origin in the link's own frame), com and
+        comvel [B, nc, 3] (world)"""
+        if not self._links_flags:
+            raise RkfdError("get_links: no read-out has been made (update_links)")
+        out = _links_arrays(self.B, self.nlink, self.nchain, self._links_flags)
+        self._chk(self._L.rkfdBatchGetLinks(self._b, *[_ptr(out.get(k)) for k, _ in _LINKS_KEYS]))
+        return out
+
+    def dev_tensors(self, links=False):
         """torch tensors ALIASING the live device state [B, ndof] (dis, vel, acc): zero-copy views
-        for consumers on the device, e.g. the RCCL all-gather of final states."""
+        for consumers on the device, e.g. the RCCL all-gather of final states.  links=True: the buffers of the task-space
+        read-out follow, likewise zero-copy - R [B, nl, 3, 3], p [B, nl, 3], v [B, nl, 6], com, comvel [B, nc, 3], None where no
+        update_links() has needed the buffer yet - always eight entries; without it always the three, whatever has been read out."""
         import torch
 
         class _View:
             def __init__(self, ptr, shape):
                 self.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(int(ptr), False), version=2, strides=None)
-        return tuple(torch.as_tensor(_View(p, (self.B, self.ndof)), device="cuda") for p in self.dev_ptrs())
+        ptrs = self.dev_ptrs(links)
+        nl, nc = self.nlink, self.nchain
+        shapes = ((self.B, self.ndof),) * 3 + ((self.B, nl, 3, 3), (self.B, nl, 3), (self.B, nl, 6), (self.B, nc, 3), (self.B, nc, 3))
+        return tuple(torch.as_tensor(_View(p, sh), device="cuda") if p else None for p, sh in zip(ptrs, shapes[:len(ptrs)]))
 
-    def dev_ptrs(self):
-        return (self._L.rkfdBatchDevDis(self._b), self._L.rkfdBatchDevVel(self._b), self._L.rkfdBatchDevAcc(self._b))
+    def links_tensors(self):
+        """the read-out's buffers alone, as a dict of zero-copy torch views (R, p, v, com, comvel; None where no update_links()
+        has needed the buffer yet)"""
+        return dict(zip([k for k, _ in _LINKS_KEYS], self.dev_tensors(links=True)[3:]))
+
+    def dev_ptrs(self, links=False):
+        """device addresses of dis, vel, acc; links=True: followed by those of the read-out's R, p, v, com, comvel (None for a
+        buffer no update_links() has needed yet; stable once allocated)"""
+        st = (self._L.rkfdBatchDevDis(self._b), self._L.rkfdBatchDevVel(self._b), self._L.rkfdBatchDevAcc(self._b))
+        if not links:
+            return st
+        return st + tuple(getattr(self._L, f)(self._b) for f in ("rkfdBatchDevLinkAtt", "rkfdBatchDevLinkPos", "rkfdBatchDevLinkVel", "rkfdBatchDevCom", "rkfdBatchDevComVel"))
 
 
 class Node:
@@ -467,7 +520,7 @@ class Node:
         self._L = lib()
         self.world = world
         m = world.model.contents
-        self.total, self.ndof, self.nlink = total, m.ndof, m.nlink
+        self.total, self.ndof, self.nlink, self.nchain = total, m.ndof, m.nlink, m.nchain
         dv = None
         if devices is not None:
             dv = (C.c_int * len(devices))(*devices); ndev = len(devices)
@@ -559,6 +612,13 @@ class Node:
 
     def status(self):
         return self._chk(self._L.rkfdNodeStatus(self._n))
+
+    def get_links(self, flags=LINKS_ALL):
+        """Batch.update_links(flags) on every device's own thread and stream, then the results of ALL instances in instance
+        order, as Batch.get_links() returns them"""
+        out = _links_arrays(self.total, self.nlink, self.nchain, int(flags))
+        self._chk(self._L.rkfdNodeGetLinks(self._n, int(flags), *[_ptr(out.get(k)) for k, _ in _LINKS_KEYS]))
+        return out
 
     def gather(self):
         """one RCCL all-gather of the final {dis, vel}; returns them on the host, [total, ndof] each"""

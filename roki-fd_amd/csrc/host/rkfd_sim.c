@@ -17,6 +17,11 @@ typedef struct {
   int status;
   int ncell;
   int bad_ode;        /* an integrator without a device path was asked for (rkFDODE2Assign*) */
+  /* rkfdChainLinkWldPos / Att / WldCOM: host copies of one device read-out (rkfdBatchUpdateLinks), made by the first such call
+   * after an rkFDUpdateInit / rkFDUpdate and reused until the next; drivers that never ask pay nothing */
+  int links_valid;
+  int lk_nl, lk_nc;   /* links and chains of the batch the read-out was made from */
+  double *lk_R, *lk_p, *lk_com;
 } rkFDImpl;
 
 typedef struct { int kind; int max_rigid; } rkFDSolverPrpAMD;
@@ -121,7 +126,7 @@ static bool solver_init(rkFDSolver *s)
   rkFD *fd = s->fd;
   rkFDImpl *im = IMPL( fd );
   rkFDSolverPrpAMD *p = (rkFDSolverPrpAMD *)s->prp;
-  if( im->batch ){ rkfdBatchDestroy( im->batch ); im->batch = NULL; }
+  if( im->batch ){ rkfdBatchDestroy( im->batch ); im->batch = NULL; im->links_valid = 0; }
   if( !rkFDBuildModel( fd ) ) return false;
   {
     /* rigid contact capacity of the single-instance path: 16 vertices; under the Vert plugin one
@@ -147,7 +152,7 @@ static void solver_update_ref(rkFDSolver *s){ (void)s; /* prev driving torque is
 static void solver_destroy(rkFDSolver *s)
 {
   rkFDImpl *im = IMPL( s->fd );
-  if( im->batch ){ rkfdBatchDestroy( im->batch ); im->batch = NULL; }
+  if( im->batch ){ rkfdBatchDestroy( im->batch ); im->batch = NULL; im->links_valid = 0; }
 }
 static void defci_volume(rkFDSolver *s, rkContactInfo *ci)
 { /* reference src/rkfd_volume.c:942-950 */
@@ -203,6 +208,7 @@ void rkFDDestroy(rkFD *fd)
   rkFDCell *c, *n;
   if( !im ) return;
   if( im->batch ) rkfdBatchDestroy( im->batch );
+  free( im->lk_R ); free( im->lk_p ); free( im->lk_com );
   rkFDSolverDestroy( &fd->solver );
   for( c=fd->list; c; c=n ){ n = c->next; free( c->chain.joint ); free( c->shape ); free( c ); }
   zVecFree( fd->dis ); zVecFree( fd->vel ); zVecFree( fd->acc );
@@ -297,7 +303,7 @@ bool rkFDChainUnreg(rkFD *fd, rkFDCell *cell)
   *pp = lc->next;
   rkfdWorldRemoveChain( &im->world, lc->chain.id );
   free( lc->chain.joint ); free( lc->shape ); free( lc );
-  if( im->batch ){ rkfdBatchDestroy( im->batch ); im->batch = NULL; }
+  if( im->batch ){ rkfdBatchDestroy( im->batch ); im->batch = NULL; im->links_valid = 0; }
   im->dirty = 1; im->ncell--;
   return true;
 }
@@ -441,6 +447,7 @@ void rkFDUpdateInit(rkFD *fd)
   }
   report( fd );
   rkfdBatchGetState( im->batch, NULL, NULL, fd->acc->buf );
+  im->links_valid = 0;
 }
 
 rkFD *rkFDUpdate(rkFD *fd)
@@ -459,8 +466,64 @@ rkFD *rkFDUpdate(rkFD *fd)
   }
   report( fd );
   rkfdBatchGetState( im->batch, fd->dis->buf, fd->vel->buf, fd->acc->buf );
+  im->links_valid = 0;
   fd->t += rkFDDT( fd );
   return fd;
+}
+
+/* ---- world frames of links and chain centres of mass (RoKi's rkChainLinkWldPos / rkChainLinkWldAtt / rkChainWldCOM), read off
+ * the device: the state they describe is the one the last rkFDUpdateInit / rkFDUpdate left there */
+static int links_refresh(rkFD *fd)
+{
+  rkFDImpl *im = IMPL( fd );
+  if( im->links_valid ) return 0;
+  if( !im->batch ){ fprintf( stderr, "rkfd: link frames asked for without a device batch (rkFDUpdateInit failed or missing)\n" ); return -1; }
+  const int nl = rkfdBatchLinkNum( im->batch ), nc = rkfdBatchChainNum( im->batch );
+  double *R = (double *)realloc( im->lk_R, sizeof(double)*9*( nl > 0 ? nl : 1 ) );
+  if( R ) im->lk_R = R;
+  double *p = (double *)realloc( im->lk_p, sizeof(double)*3*( nl > 0 ? nl : 1 ) );
+  if( p ) im->lk_p = p;
+  double *c = (double *)realloc( im->lk_com, sizeof(double)*3*( nc > 0 ? nc : 1 ) );
+  if( c ) im->lk_com = c;
+  if( !R || !p || !c ){ fprintf( stderr, "rkfd: out of memory\n" ); return -1; }
+  if( rkfdBatchUpdateLinks( im->batch, RKFD_LINKS_POSE | RKFD_LINKS_COM, NULL ) < 0 ||
+      rkfdBatchGetLinks( im->batch, im->lk_R, im->lk_p, NULL, im->lk_com, NULL ) < 0 ){
+    fprintf( stderr, "rkfd: %s\n", rkfdHipLastError() );
+    return -1;
+  }
+  im->lk_nl = nl; im->lk_nc = nc;
+  im->links_valid = 1;
+  return 0;
+}
+/* the read-out describes the world of the last rkFDUpdateInit: a chain registered since is not part of it */
+static int links_has(rkChain *c, int link)
+{
+  rkFDImpl *im;
+  if( !c || !c->fd || link < 0 || link >= c->nlink || links_refresh( c->fd ) < 0 ) return 0;
+  im = IMPL( c->fd );
+  if( c->id < 0 || c->id >= im->lk_nc || c->link_off < 0 || c->link_off + link >= im->lk_nl ){
+    fprintf( stderr, "rkfd: link frames asked for a chain that was not part of the last rkFDUpdateInit\n" );
+    return 0;
+  }
+  return 1;
+}
+void rkfdChainLinkWldPos(rkChain *c, int link, double p[3])
+{
+  p[0] = p[1] = p[2] = 0;
+  if( !links_has( c, link ) ) return;
+  memcpy( p, IMPL( c->fd )->lk_p + 3*( c->link_off + link ), sizeof(double)*3 );
+}
+void rkfdChainLinkWldAtt(rkChain *c, int link, double R[9])
+{
+  for( int k=0; k<9; k++ ) R[k] = ( k%4 == 0 ) ? 1.0 : 0.0;
+  if( !links_has( c, link ) ) return;
+  memcpy( R, IMPL( c->fd )->lk_R + 9*( c->link_off + link ), sizeof(double)*9 );
+}
+void rkfdChainWldCOM(rkChain *c, double com[3])
+{
+  com[0] = com[1] = com[2] = 0;
+  if( !links_has( c, 0 ) ) return;
+  memcpy( com, IMPL( c->fd )->lk_com + 3*c->id, sizeof(double)*3 );
 }
 
 void rkFDUpdateDestroy(rkFD *fd)

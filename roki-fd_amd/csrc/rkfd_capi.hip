@@ -17,6 +17,7 @@
 #include "rkfd_hip.h"
 #include "rkfd_device.h"
 #include "rkfd_devmodel_host.h"
+#include "readout/rkfd_links_host.h"   /* the task-space read-out (rkfd_capi_links.hip) */
 #include "rkfd_device_src.inc"       /* the device headers as string literals (tools/embed_sources.py), for hipRTC */
 
 static thread_local char g_err[512] = "";
@@ -154,6 +155,10 @@ struct rkfdBatch {
   double *h_par[RKFD_PAR_COUNT];
   double *d_par;
   int par_stride;
+  /* rkfdBatchUpdateLinks: the task-space read-out's tables and result buffers (rkfd_capi_links.hip), made by the first read-out -
+   * a batch that never asks has none; par_gen counts the changes of the parameter table (the read-out keeps model-space rows of its own) */
+  rkfdLinks *links;
+  int par_gen;
 };
 
 extern "C" const char *rkfdHipLastError(void){ return g_err; }
@@ -261,6 +266,7 @@ extern "C" void rkfdBatchDestroy(rkfdBatch *b)
   for( int k=0; k<RKFD_MAX_SPLIT; k++ ) if( b->ctrl_ev[k] ) (void)hipEventDestroy( b->ctrl_ev[k] );
   (void)hipFree( b->d_ctrl ); if( b->h_ctrl ) (void)hipHostFree( b->h_ctrl );
   (void)hipFree( b->d_par ); for( int k=0; k<RKFD_PAR_COUNT; k++ ) free( b->h_par[k] );
+  rkfd_links_destroy( b->links );
   if( b->spec_mod ) (void)hipModuleUnload( b->spec_mod );
   (void)hipFree( b->d_err ); (void)hipFree( b->dblob ); (void)hipFree( b->dblob2 );
   rkfd_devmodel_free( &b->host ); rkfd_devmodel_free( &b->host2 );
@@ -1093,6 +1099,7 @@ extern "C" int rkfdBatchSetParam(rkfdBatch *b, int which, const double *values)
     for( int k=0; k<RKFD_PAR_COUNT; k++ ) h[k] = k == which ? nk : b->h_par[k];
     if( par_upload( b, h, b->d_par, (size_t)b->par_stride ) < 0 ){ free( nk ); return -1; }
     free( b->h_par[which] ); b->h_par[which] = nk;
+    b->par_gen++;
     return 0;
   }
   if( !values ) return 0;      /* no table: every key is the model's already */
@@ -1122,7 +1129,7 @@ extern "C" int rkfdBatchSetParam(rkfdBatch *b, int which, const double *values)
     return -1;
   }
   for( int k=0; k<RKFD_PAR_COUNT; k++ ) b->h_par[k] = h[k];
-  b->d_par = d; b->par_stride = (int)stride;
+  b->d_par = d; b->par_stride = (int)stride; b->par_gen++;
   if( fn ){ (void)hipModuleUnload( b->spec_mod ); b->spec_mod = mod; b->spec_fn = fn; b->spec_par = 1; }
   return 0;
 }
@@ -1145,7 +1152,7 @@ extern "C" int rkfdBatchClearParams(rkfdBatch *b)
   hipModule_t mod = NULL; hipFunction_t fn = NULL;
   if( b->spec_fn && spec_build( b, 0, &mod, &fn ) < 0 ) return -1;
   if( fn ){ (void)hipModuleUnload( b->spec_mod ); b->spec_mod = mod; b->spec_fn = fn; b->spec_par = 0; }
-  (void)hipFree( b->d_par ); b->d_par = NULL; b->par_stride = 0;
+  (void)hipFree( b->d_par ); b->d_par = NULL; b->par_stride = 0; b->par_gen++;
   for( int k=0; k<RKFD_PAR_COUNT; k++ ){ free( b->h_par[k] ); b->h_par[k] = NULL; }
   return 0;
 }
@@ -1271,5 +1278,47 @@ extern "C" int rkfdBatchRestore(rkfdBatch *b, void *stream)
   b->pending = 1;
   return 0;
 }
+
+/* ---- task-space read-out: link poses, velocities and chain COM on the device ---------------------------------- */
+extern "C" int rkfdBatchLinkNum(const rkfdBatch *b){ return b ? b->nlink : -1; }
+extern "C" int rkfdBatchChainNum(const rkfdBatch *b){ return b ? b->model_for_w2->nchain : -1; }
+/* One launch of rkfd_links_kernel in stream order after everything the batch has launched: the internal split streams are joined
+ * onto `stream` first (as rkfdBatchJoin does), no host wait.  It reads dis / vel and writes the read-out's own buffers only. */
+extern "C" int rkfdBatchUpdateLinks(rkfdBatch *b, int flags, void *stream)
+{
+  if( !b ){ SETERR( "rkfdBatchUpdateLinks: null batch" ); return -1; }
+  if( flags <= 0 || ( flags & ~( RKFD_LINKS_POSE | RKFD_LINKS_VEL | RKFD_LINKS_COM ) ) ){ SETERR( "rkfdBatchUpdateLinks: flags must be a combination of RKFD_LINKS_POSE, RKFD_LINKS_VEL and RKFD_LINKS_COM (got %d)", flags ); return -1; }
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  char err[400] = "";
+  if( !b->links ){
+    b->links = rkfd_links_create( b->model_for_w2, &b->host, &b->dm, b->batch, err, sizeof(err) );
+    if( !b->links ){ SETERR( "%s", err ); return -1; }
+  }
+  if( join_streams( b, (hipStream_t)stream ) < 0 ) return -1;
+  b->last_stream = (hipStream_t)stream;
+  if( rkfd_links_launch( b->links, b->st.dis, b->st.vel, flags, b->d_par ? b->h_par[RKFD_PAR_MASS] : NULL, b->d_par ? b->h_par[RKFD_PAR_COM] : NULL,
+                         b->par_gen, stream, err, sizeof(err) ) < 0 ){ SETERR( "rkfdBatchUpdateLinks: %s", err ); return -1; }
+  return 0;
+}
+extern "C" int rkfdBatchGetLinks(rkfdBatch *b, double *R, double *p, double *v, double *com, double *comvel)
+{
+  if( !b ){ SETERR( "rkfdBatchGetLinks: null batch" ); return -1; }
+  const int have = rkfd_links_flags( b->links );
+  if( !have ){ SETERR( "rkfdBatchGetLinks: no read-out has been made (rkfdBatchUpdateLinks)" ); return -1; }
+  if( ( ( R || p ) && !( have & RKFD_LINKS_POSE ) ) || ( v && !( have & RKFD_LINKS_VEL ) ) || ( ( com || comvel ) && !( have & RKFD_LINKS_COM ) ) ){
+    SETERR( "rkfdBatchGetLinks: the last rkfdBatchUpdateLinks (flags %d) did not compute %s", have,
+            ( ( R || p ) && !( have & RKFD_LINKS_POSE ) ) ? "the poses (RKFD_LINKS_POSE)" : ( v && !( have & RKFD_LINKS_VEL ) ) ? "the velocities (RKFD_LINKS_VEL)" : "the centres of mass (RKFD_LINKS_COM)" );
+    return -1;
+  }
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  char err[400] = "";
+  if( rkfd_links_get( b->links, R, p, v, com, comvel, err, sizeof(err) ) < 0 ){ SETERR( "rkfdBatchGetLinks: %s", err ); return -1; }
+  return 0;
+}
+extern "C" const double *rkfdBatchDevLinkAtt(rkfdBatch *b){ return b ? rkfd_links_dev( b->links, 0 ) : NULL; }
+extern "C" const double *rkfdBatchDevLinkPos(rkfdBatch *b){ return b ? rkfd_links_dev( b->links, 1 ) : NULL; }
+extern "C" const double *rkfdBatchDevLinkVel(rkfdBatch *b){ return b ? rkfd_links_dev( b->links, 2 ) : NULL; }
+extern "C" const double *rkfdBatchDevCom(rkfdBatch *b){ return b ? rkfd_links_dev( b->links, 3 ) : NULL; }
+extern "C" const double *rkfdBatchDevComVel(rkfdBatch *b){ return b ? rkfd_links_dev( b->links, 4 ) : NULL; }
 
 #include "rkfd_capi_node.inc"      /* the node level: one host thread + stream per device, one RCCL all-gather of final states */

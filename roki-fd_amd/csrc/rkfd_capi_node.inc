@@ -48,7 +48,7 @@ static const rkfdRccl *rccl_api(void)
   return state == 1 ? &api : NULL;
 }
 
-enum { NODE_CMD_NONE = 0, NODE_CMD_INIT, NODE_CMD_UPDATE, NODE_CMD_SPECIALIZE, NODE_CMD_SPLIT, NODE_CMD_STEPS_PER_LAUNCH, NODE_CMD_TUNE, NODE_CMD_STATUS, NODE_CMD_SNAPSHOT, NODE_CMD_RESTORE, NODE_CMD_PACK, NODE_CMD_UPDATE_CTRL, NODE_CMD_QUIT };
+enum { NODE_CMD_NONE = 0, NODE_CMD_INIT, NODE_CMD_UPDATE, NODE_CMD_SPECIALIZE, NODE_CMD_SPLIT, NODE_CMD_STEPS_PER_LAUNCH, NODE_CMD_TUNE, NODE_CMD_STATUS, NODE_CMD_SNAPSHOT, NODE_CMD_RESTORE, NODE_CMD_PACK, NODE_CMD_UPDATE_CTRL, NODE_CMD_LINKS, NODE_CMD_QUIT };
 
 struct rkfdNode;
 struct rkfdNodeWorker {
@@ -83,6 +83,7 @@ static int node_run_on(rkfdNode *n, int k, int cmd, int arg)
   case NODE_CMD_INIT:       return rkfdBatchUpdateInit( b, n->st[k] );
   case NODE_CMD_UPDATE:     return rkfdBatchUpdate( b, arg, n->st[k] );
   case NODE_CMD_UPDATE_CTRL: return rkfdBatchUpdateControlled( b, arg, n->ctrl + (size_t)n->lo[k]*arg*n->nlink, n->st[k] );
+  case NODE_CMD_LINKS:      return rkfdBatchUpdateLinks( b, arg, n->st[k] );
   case NODE_CMD_SPECIALIZE: return rkfdBatchSpecialize( b );
   case NODE_CMD_SPLIT:      return rkfdBatchSetSplit( b, arg );
   case NODE_CMD_STEPS_PER_LAUNCH: return rkfdBatchSetStepsPerLaunch( b, arg );
@@ -292,6 +293,20 @@ extern "C" int rkfdNodeUpdateControlled(rkfdNode *n, int nsteps, const double *u
   const int r = node_all( n, NODE_CMD_UPDATE_CTRL, nsteps );
   n->ctrl = NULL;
   return r;
+}
+
+/* the task-space read-out over all instances: rkfdBatchUpdateLinks on every device's own thread and stream, then the host arrays
+ * in instance order (the pointers of quantities `flags` does not select must be NULL) */
+extern "C" int rkfdNodeGetLinks(rkfdNode *n, int flags, double *R, double *p, double *v, double *com, double *comvel)
+{
+  if( !n ){ SETERR( "rkfdNodeGetLinks: null node" ); return -1; }
+  if( node_all( n, NODE_CMD_LINKS, flags ) < 0 ) return -1;
+  for( int k=0; k<n->ndev; k++ ){
+    const size_t lo = (size_t)n->lo[k], nl = (size_t)n->nlink, nc = (size_t)rkfdBatchChainNum( n->b[k] );
+    if( rkfdBatchGetLinks( n->b[k], R ? R + lo*nl*9 : NULL, p ? p + lo*nl*3 : NULL, v ? v + lo*nl*6 : NULL,
+                           com ? com + lo*nc*3 : NULL, comvel ? comvel + lo*nc*3 : NULL ) < 0 ) return -1;
+  }
+  return 0;
 }
 
 /* the path's only collective: every device contributes its block of final {dis, vel} ([mx][2 ndof] doubles, its own instances

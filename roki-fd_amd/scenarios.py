@@ -104,9 +104,11 @@ def link_frames(m, Q):
             R[:, i] = Rp @ Ro @ Rz; p[:, i] = pp + Rp @ po
         elif jt[i] == B.JOINT_PRISM:
             R[:, i] = Rp @ Ro; p[:, i] = pp + np.einsum("bij,bj->bi", Rp, po + Ro[:, 2][None] * Q[:, off[i]][:, None])
-        elif jt[i] == B.JOINT_FLOAT:
+        elif jt[i] in (B.JOINT_FLOAT, B.JOINT_BRFLOAT):      # (a breakable float joint sits where its six coordinates put it, broken or not)
             R[:, i] = Rp @ Ro @ _rot_aa_batch(Q[:, off[i] + 3:off[i] + 6])
             p[:, i] = pp + np.einsum("bij,bj->bi", Rp, po + Q[:, off[i]:off[i] + 3] @ Ro.T)
+        elif jt[i] == B.JOINT_SPHER:
+            R[:, i] = Rp @ Ro @ _rot_aa_batch(Q[:, off[i]:off[i] + 3]); p[:, i] = pp + Rp @ po
         else:
             R[:, i] = Rp @ Ro; p[:, i] = pp + Rp @ po
     return R, p
