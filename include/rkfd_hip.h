@@ -43,6 +43,14 @@ void rkfdBatchDestroy(rkfdBatch *b);
 int rkfdBatchSize(const rkfdBatch *b);
 int rkfdBatchDof(const rkfdBatch *b);
 
+/* The Set / Get accessors below are SYNCHRONOUS and ordered after the batch's launches: each waits for the batch's internal
+ * (split) streams and for the stream its LAST launch was given (rkfdBatchUpdateInit / Update / UpdateControlled[Dev] / Eval /
+ * Restore / UpdateLinks) before it copies - also when that stream was made with hipStreamNonBlocking, which the null stream of the
+ * copies is not ordered against.  A value set is seen by every launch made after the call returns; a value read is what the
+ * launches made before the call left.  Launches a caller spread over FURTHER streams of its own must be joined by the caller first
+ * (rkfdBatchStatus on each, or its own events): only the stream of the last launch is known to the batch.  That stream must
+ * still exist at the first accessor (or rkfdBatchStatus on it) after the launch: destroy it only after one of them has returned.
+ * An error the launch left on the stream is the accessor's error. */
 /* rkFDChainSetDis / rkFDChainSetVel (reference src/rkfd_sim.c:277-287), all instances at once:
  * dis, vel are [batch][ndof] */
 int rkfdBatchSetState(rkfdBatch *b, const double *dis, const double *vel);
@@ -88,7 +96,8 @@ int rkfdBatchEval(rkfdBatch *b, int doUpRef, void *stream);
  * instances are independent, so the parts need not wait for each other: the thinly occupied tail of one
  * step of one part then overlaps the next step of another (+20 % at 4096 instances per GPU).  The parts start
  * after whatever `stream` holds at the time of the call; `stream` itself does NOT wait for them until
- * rkfdBatchJoin( b, stream ) or rkfdBatchStatus( b, stream ); the host-side accessors (Get / Set) wait.
+ * rkfdBatchJoin( b, stream ) or rkfdBatchStatus( b, stream ); the host-side accessors (Get / Set) wait for the internal
+ * streams and for `stream` of the last launch, at every nsplit.
  * nsplit = 1 (default): one launch on the caller's stream, plain stream order. */
 int rkfdBatchSetSplit(rkfdBatch *b, int nsplit);
 /* Under split launches a call of n steps goes out as rounds of launches of at most `steps` steps each (default 5; worlds under
@@ -268,7 +277,9 @@ int rkfdNodeSize(const rkfdNode *n);
 /* shard k: its HIP device and its block of instances [lo, hi); the rkfdBatch behind it (for the per-batch accessors) */
 int rkfdNodeShard(const rkfdNode *n, int k, int *device, int *lo, int *hi);
 rkfdBatch *rkfdNodeBatch(rkfdNode *n, int k);
-/* host arrays over ALL instances, [total][ndof] / [total][nlink]: scattered to / collected from the devices' shards */
+/* host arrays over ALL instances, [total][ndof] / [total][nlink]: scattered to / collected from the devices' shards; ordered after
+ * the node's launches like the rkfdBatch accessors (each shard waits for its device's stream), as are the per-batch accessors on
+ * rkfdNodeBatch( n, k ) */
 int rkfdNodeSetState(rkfdNode *n, const double *dis, const double *vel);
 int rkfdNodeSetMotorInput(rkfdNode *n, const double *input);
 int rkfdNodeGetState(rkfdNode *n, double *dis, double *vel, double *acc);      /* plain copies, no collective; any may be NULL */

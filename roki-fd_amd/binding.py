@@ -243,7 +243,8 @@ class Batch:
     """B instances of one world on one GPU (include/rkfd_hip.h).  All arrays are
     instance-major numpy arrays [B, ...]."""
 
-    def __init__(self, world, batch, device=0, max_rigid=8):
+    def __init__(self, world, batch, device=0, max_rigid=8, _handle=None):
+        """_handle: an rkfdBatch that someone else owns (Node.batch) - close() then only forgets it"""
         self._L = lib()
         self.world = world
         m = world.model.contents
@@ -252,13 +253,15 @@ class Batch:
         self._links_flags = 0          # what the last update_links() computed
         self.device = device
         self._ctrl_keep = []           # device schedules of update_controlled() the launches issued since the last join / sync read
-        self._b = self._L.rkfdBatchCreate(world.model, batch, device, max_rigid)
+        self._owned = _handle is None
+        self._b = self._L.rkfdBatchCreate(world.model, batch, device, max_rigid) if self._owned else _handle
         if not self._b:
             raise RkfdError(self._L.rkfdHipLastError().decode())
 
     def close(self):
         if getattr(self, "_b", None):
-            self._L.rkfdBatchDestroy(self._b)
+            if self._owned:
+                self._L.rkfdBatchDestroy(self._b)
             self._b = None
 
     def __del__(self):
@@ -552,6 +555,14 @@ class Node:
             self._chk(self._L.rkfdNodeShard(self._n, k, C.byref(d), C.byref(lo), C.byref(hi)))
             out.append((d.value, lo.value, hi.value))
         return out
+
+    def batch(self, k):
+        """the Batch behind shard k (rkfdNodeBatch), for the per-batch accessors: a view - the node keeps owning it, and it must
+        not be used after the node is closed"""
+        if not 0 <= k < self.ndev:
+            raise RkfdError(f"no shard {k} (the node has {self.ndev})")
+        dev, lo, hi = self.shards()[k]
+        return Batch(self.world, hi - lo, device=dev, _handle=self._L.rkfdNodeBatch(self._n, k))
 
     def set_state(self, dis, vel):
         dis = np.ascontiguousarray(dis, dtype=np.float64).reshape(self.total, self.ndof)

@@ -122,7 +122,8 @@ struct rkfdBatch {
   /* rkfdBatchSpecialize: the step kernel compiled for this world (hipRTC); NULL = the generic kernels above */
   hipModule_t spec_mod;
   hipFunction_t spec_fn;
-  hipStream_t last_stream;   /* the caller's stream of the last launch: what rkfdBatchSetParam / ClearParams wait for besides the internal streams */
+  hipStream_t last_stream;   /* the caller's stream of the last launch: what the synchronous accessors wait for besides the internal streams */
+  int launched;              /* work went to last_stream that no accessor has waited for yet */
   int spec_par;              /* 1: spec_fn was compiled with RKFD_PARAMS = 1 (the batch carried a table when it was made) */
   /* rkfdBatchSetInstancesPerWave( b, 2 ): a second device model (sweep schedule with four links per iteration) for the
    * world-specific kernel built with RKFD_W = 2 - two instances per wavefront, 32 lanes each */
@@ -442,11 +443,16 @@ static int join_streams(rkfdBatch *b, hipStream_t stream)
   }
   return 0;
 }
-/* host waits for the internal streams (used by the synchronous accessors) */
+/* host waits for the internal streams and for the caller's stream of the batch's last launch (used by the synchronous accessors:
+ * their blocking copies go over the null stream, which a stream made with hipStreamNonBlocking - the node level's, torch's - is not
+ * ordered against).  Launches a caller spread over FURTHER streams of its own must be joined by the caller first. */
 static int sync_streams(rkfdBatch *b)
 {
   if( b->nsplit > 1 ) for( int k=0; k<b->nsplit; k++ ) HIPCHK( hipStreamSynchronize( b->sub[k] ), -1 );
   b->pending = 0;
+  /* (the stream of the last launch must still exist here - include/rkfd_hip.h; once waited for, by this or by rkfdBatchStatus on
+   *  it, it is not touched again until the next launch names one) */
+  if( b->launched ){ HIPCHK( hipStreamSynchronize( b->last_stream ), -1 ); b->launched = 0; }
   return 0;
 }
 /* the device model a launch passes: with a table of per-instance parameters, the pointers to those parameters point at its first
@@ -505,7 +511,7 @@ static int launch(rkfdBatch *b, int mode, int nsteps, void *stream, const double
   if( !b ){ SETERR( "null batch" ); return -1; }
   HIPCHK( hipSetDevice( b->device ), -1 );
   rkfdKernel kern = b->st.prof ? b->kern_prof : b->kern;
-  b->last_stream = (hipStream_t)stream;
+  b->last_stream = (hipStream_t)stream; b->launched = 1;
   const int cstride = ctrl ? nsteps*b->nlink : 0;
   if( b->nsplit <= 1 || b->st.prof ){
     if( b->st.prof && sync_streams( b ) < 0 ) return -1;
@@ -1060,12 +1066,7 @@ static int par_check(const rkfdBatch *b, int which, const double *values)
 }
 /* what the table's launches may still be reading: the internal streams and the caller's stream of the last launch (launches a
  * caller made on OTHER streams of its own must be joined by the caller first: rkfdBatchJoin / rkfdBatchStatus) */
-static int par_quiesce(rkfdBatch *b)
-{
-  if( sync_streams( b ) < 0 ) return -1;
-  HIPCHK( hipStreamSynchronize( b->last_stream ), -1 );
-  return 0;
-}
+static int par_quiesce(rkfdBatch *b){ return sync_streams( b ); }
 /* the device table from a host copy h[key][batch][width]: every instance's row through rkfd_devmodel_par_row */
 static int par_upload(rkfdBatch *b, double *const *h, double *d, size_t stride)
 {
@@ -1184,6 +1185,7 @@ extern "C" int rkfdBatchStatus(rkfdBatch *b, void *stream)
   HIPCHK( hipSetDevice( b->device ), -1 );
   if( join_streams( b, (hipStream_t)stream ) < 0 ) return -1;
   HIPCHK( hipStreamSynchronize( (hipStream_t)stream ), -1 );
+  if( (hipStream_t)stream == b->last_stream ) b->launched = 0;
   int e = 0;
   HIPCHK( hipMemcpy( &e, b->d_err, sizeof(int), hipMemcpyDeviceToHost ), -1 );
   if( e == 1 ){
@@ -1259,6 +1261,7 @@ extern "C" int rkfdBatchRestore(rkfdBatch *b, void *stream)
   if( !b ){ SETERR( "null batch" ); return -1; }
   if( !b->has_snap ){ SETERR( "rkfdBatchRestore: no snapshot has been taken (rkfdBatchSnapshot)" ); return -1; }
   HIPCHK( hipSetDevice( b->device ), -1 );
+  b->last_stream = (hipStream_t)stream; b->launched = 1;
   if( b->nsplit <= 1 ){
     hipLaunchKernelGGL( rkfd_restore_kernel, dim3( b->batch ), dim3( RKFD_WAVE ), 0, (hipStream_t)stream, b->st, b->snap, 0, b->ndof, b->nlink, b->ncand );
     HIPCHK( hipGetLastError(), -1 );
@@ -1295,7 +1298,7 @@ extern "C" int rkfdBatchUpdateLinks(rkfdBatch *b, int flags, void *stream)
     if( !b->links ){ SETERR( "%s", err ); return -1; }
   }
   if( join_streams( b, (hipStream_t)stream ) < 0 ) return -1;
-  b->last_stream = (hipStream_t)stream;
+  b->last_stream = (hipStream_t)stream; b->launched = 1;
   if( rkfd_links_launch( b->links, b->st.dis, b->st.vel, flags, b->d_par ? b->h_par[RKFD_PAR_MASS] : NULL, b->d_par ? b->h_par[RKFD_PAR_COM] : NULL,
                          b->par_gen, stream, err, sizeof(err) ) < 0 ){ SETERR( "rkfdBatchUpdateLinks: %s", err ); return -1; }
   return 0;
