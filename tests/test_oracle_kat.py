@@ -64,6 +64,33 @@ def test_aba_vs_newton_euler_float_humanoid(R, oracle_cls, humanoid_nomotor):
         assert np.abs(rm.rnea(md, q, qd, qdd)).max() < 1e-10 * max(1.0, np.abs(qdd).max())
 
 
+def test_aba_vs_newton_euler_float_humanoid_with_motors(R, oracle_cls):
+    """(2) the same with the humanoid's DC motors driven (inputs beyond the +-24 V limits too): input torque, back-EMF torque and
+    the rotor inertia reflected through the gear (refmath.actuator_torque, [UNVERIFIED-DEP] DEVIATIONS.md item 5).  A DC-motor
+    joint with joint friction carries a friction torque nobody reports: on its coordinate the balance is held to the limit the
+    reference's rule leaves for the pivot state (src/rkfd_util.c:345-352), every other coordinate must close"""
+    w, _ = _world(R, ["humanoid30.ztk"], solver=R.SOLVER_VERT)
+    m = w.model.contents
+    md = rm.model_arrays(m)
+    o = oracle_cls(w.model)
+    rng = np.random.default_rng(8)
+    closed = 0
+    for _ in range(4):
+        q = rng.uniform(-1, 1, 30); qd = rng.uniform(-2, 2, 30); inp = rng.uniform(-30, 30, m.nlink)
+        o.set_state(q, qd); o.set_motor_input(inp); assert o.eval(False) == 0
+        qdd = o.get_state()[2]; piv = o.get_pivot()[0]
+        r = rm.rnea(md, q, qd, qdd) - rm.actuator_torque(md, qd, qdd, inp)
+        tol = 1e-10 * max(1.0, np.abs(qdd).max())
+        for l in range(m.nlink):
+            for k in range(md["dofoff"][l], md["dofoff"][l] + (6 if md["jtype"][l] == rm.FLOAT else int(md["jtype"][l] in (rm.REVOL, rm.PRISM)))):
+                if md["mtype"][l] == rm.MOTOR_DC and (md["stiff"][l] or md["visc"][l] or md["coulomb"][l] or md["sfric"][l]):
+                    fmax = md["sfric"][l] if piv[l] == 0 else abs(md["stiff"][l] * q[k] + md["visc"][l] * qd[k] + md["coulomb"][l] * np.sign(qd[k]))
+                    assert abs(r[k]) <= abs(fmax) + tol, (l, r[k], fmax)
+                else:
+                    assert abs(r[k]) < tol, (l, r[k]); closed += 1
+    assert closed >= 24 and (md["mtype"] == rm.MOTOR_DC).any()
+
+
 def test_probed_matrix_is_J_Minv_JT(R, oracle_cls, humanoid_nomotor):
     """(3) the column-by-column probed contact matrix equals J M^-1 J' + L, symmetric PSD"""
     w, (h, f) = _world(R, [humanoid_nomotor, "floor.ztk"], "contact_rigid.ztk")
