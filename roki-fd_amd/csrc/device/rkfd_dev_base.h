@@ -153,7 +153,8 @@ template<int C> RKFD_DEV void rkfd_rowbc_fmac(double &acc, double x, double a)
 #else
 #  define BCASTI(x,l)   rkfd_bcasti( (int)(x), l )
 /* the votes of the instance's own half, in bits 0 .. 31 (a per-lane value: what is branched on it diverges between the halves,
- * which the compiler handles with the execution mask) */
+ * which the compiler handles with the execution mask; tests/test_gpu_mixed.py stands behind that: every ordered pair of unlike
+ * instances - airborne beside standing, breaking beside whole - in one wavefront, each bit for bit what it gives alone) */
 #  define BALLOT(p)     ( ( __ballot(p) >> ( (int)threadIdx.x & 32 ) ) & 0xffffffffull )
 #endif
 /* sum / minimum over the whole wave in registers, the same value in every lane: the 8-lane DPP butterfly, then the eight
