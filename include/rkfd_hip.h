@@ -45,7 +45,7 @@ int rkfdBatchDof(const rkfdBatch *b);
 
 /* The Set / Get accessors below are SYNCHRONOUS and ordered after the batch's launches: each waits for the batch's internal
  * (split) streams and for the stream its LAST launch was given (rkfdBatchUpdateInit / Update / UpdateControlled[Dev] / Eval /
- * Restore / UpdateLinks) before it copies - also when that stream was made with hipStreamNonBlocking, which the null stream of the
+ * Restore / Reset[Dev] / UpdateLinks) before it copies - also when that stream was made with hipStreamNonBlocking, which the null stream of the
  * copies is not ordered against.  A value set is seen by every launch made after the call returns; a value read is what the
  * launches made before the call left.  Launches a caller spread over FURTHER streams of its own must be joined by the caller first
  * (rkfdBatchStatus on each, or its own events): only the stream of the last launch is known to the batch.  That stream must
@@ -155,7 +155,8 @@ int rkfdBatchLaunchTiming(rkfdBatch *b, int *launches, double *total_ms);
  * out of iterations (256) or of basis history (64), 4 Volume plugin: a GUARDED pair came into contact - a rigid pair with a
  * shape that is not convex, or with more than 64 faces together, cannot be clipped on the device; such a world is accepted
  * (the reference's humanoid mighty.ztk, whose body meshes are not convex, stands and walks on its convex soles) and the
- * plugin's own collision test watches those pairs -; negative: HIP error.  rkfdHipLastError() describes a
+ * plugin's own collision test watches those pairs -, 5 rkfdBatchReset / ResetDev: a slot value that names no row (that instance
+ * was left as it was); negative: HIP error.  rkfdHipLastError() describes a
  * non-zero status.  A condition is reported ONCE: the call clears the device-side flag, so the next status tells
  * what happened after this one (when several conditions occurred since the last call, the last one written wins). */
 int rkfdBatchStatus(rkfdBatch *b, void *stream);
@@ -173,6 +174,35 @@ int rkfdBatchContactStats(rkfdBatch *b, int reset, double *mean_rigid, double *m
  * (reference src/rkfd_sim.c:277-287) and rkFDUpdateInit. */
 int rkfdBatchSnapshot(rkfdBatch *b);
 int rkfdBatchRestore(rkfdBatch *b, void *stream);
+
+/* ---- per-instance reset on the device from a bank of start states ------------------------------------------------------
+ * rkfdBatchRestore puts EVERY instance back; an RL or sampling loop whose episodes end at different times starts ONE instance over
+ * while its neighbours run on.  The bank is `nslots` rows on the batch's device, each the complete state of one instance - what
+ * Snapshot / Restore keep: dis, vel, acc, friction pivots, broken flags, contact-vertex state, anchors and forces; motor input,
+ * parameters and the contact statistics are not state here either.  It is separate from the whole-batch snapshot, and a batch that
+ * never reserves one allocates nothing.  The rows come from LIVE instances: set K start states in K instances, rkfdBatchUpdateInit,
+ * optionally some steps, rkfdBatchBankStore - the rows then hold consistent accelerations, pivots, anchors and forces, and an
+ * instance reset from a row continues bit for bit as the stored instance did (under the same motor input and parameters).  One
+ * launch of rkfd_reset_kernel (a kernel of its own: the step kernels are untouched), one wavefront per instance; an instance that
+ * keeps its state costs one load and one branch.  The reference has no counterpart: its caller re-runs rkFDChainSetDis / SetVel
+ * (reference src/rkfd_sim.c:277-287) and rkFDUpdateInit on one rkFD; a masked rkfdBatchUpdateInit is not given (DEVIATIONS.md). */
+int rkfdBatchBankReserve(rkfdBatch *b, int nslots);   /* (re)allocates, contents undefined; 0 frees; synchronous */
+int rkfdBatchBankSize(const rkfdBatch *b);            /* 0 when none; -1 null batch */
+/* rows slot .. slot+count-1  <-  live state of instances first .. first+count-1.
+ * Synchronous and ordered after the batch's launches like rkfdBatchSnapshot. */
+int rkfdBatchBankStore(rkfdBatch *b, int slot, int first, int count);
+enum { RKFD_RESET_KEEP = -1, RKFD_RESET_SNAPSHOT = -2 };
+/* slots[batch], int32: s in [0, nslots)       -> instance i gets bank row s
+ *                     RKFD_RESET_KEEP         -> instance i is not touched
+ *                     RKFD_RESET_SNAPSHOT     -> instance i gets ITS OWN row of rkfdBatchSnapshot (a masked Restore)
+ * anything else (including SNAPSHOT when no snapshot was taken, and any s >= 0 when there is no bank): the instance is not
+ * touched and rkfdBatchStatus reports the status 5, once, like the other conditions.
+ * Asynchronous, in stream order; under split launches every part resets itself on its own internal stream, in order with its
+ * steps, as rkfdBatchRestore does. */
+int rkfdBatchReset(rkfdBatch *b, const int *slots, void *stream);        /* host array: staged in a pinned buffer of the batch before
+                                                                           the call returns, reusable at once (as the control schedule is) */
+int rkfdBatchResetDev(rkfdBatch *b, const int *slots_dev, void *stream); /* on the batch's device, read in stream order; the caller
+                                                                           keeps it unchanged until the reset is done */
 
 /* ---- per-instance physical parameters (domain randomisation) --------------------------------------------------------
  * A batch is `batch` copies of one world; these calls let every instance have its OWN link masses, centres of mass, inertias, joint
@@ -302,6 +332,13 @@ int rkfdNodeUpdateControlled(rkfdNode *n, int nsteps, const double *u);
  * rkfdNodeSetState (NULL: the key back to the model's value everywhere).  Nothing is changed on any device when one refuses. */
 int rkfdNodeSetParam(rkfdNode *n, int which, const double *values);
 int rkfdNodeClearParams(rkfdNode *n);
+/* the bank of start states on every device (replicated, like the model): rkfdNodeBankStore takes GLOBAL instance indices, reads the
+ * rows from the shards that own them and writes them to every device's bank (through the host).  rkfdNodeReset: slots[total] on the
+ * host, sharded like rkfdNodeSetState, issued on each device's own thread and stream; nothing is changed on any device when one
+ * refuses. */
+int rkfdNodeBankReserve(rkfdNode *n, int nslots);
+int rkfdNodeBankStore(rkfdNode *n, int slot, int first, int count);
+int rkfdNodeReset(rkfdNode *n, const int *slots);
 /* rkfdBatchUpdateLinks( flags ) on every device's own thread and stream, then host arrays over ALL instances in instance order
  * (shapes as rkfdBatchGetLinks with batch = total; pointers of quantities `flags` does not select must be NULL) */
 int rkfdNodeGetLinks(rkfdNode *n, int flags, double *R, double *p, double *v, double *com, double *comvel);

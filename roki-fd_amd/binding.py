@@ -111,6 +111,11 @@ def lib():
     L.rkfdBatchStatus.argtypes = [vp, vp]
     L.rkfdBatchContactStats.argtypes = [vp, C.c_int, _pd, _pd, C.POINTER(C.c_longlong)]
     L.rkfdBatchSnapshot.argtypes = [vp]; L.rkfdBatchRestore.argtypes = [vp, vp]
+    L.rkfdBatchBankReserve.argtypes = [vp, C.c_int]; L.rkfdBatchBankSize.argtypes = [vp]
+    L.rkfdBatchBankStore.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.rkfdBatchReset.argtypes = [vp, vp, vp]; L.rkfdBatchResetDev.argtypes = [vp, vp, vp]
+    L.rkfdNodeBankReserve.argtypes = [vp, C.c_int]; L.rkfdNodeBankStore.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.rkfdNodeReset.argtypes = [vp, vp]
     L.rkfdBatchProfile.argtypes = [vp, C.c_int, vp]
     L.rkfdBatchSetSplit.argtypes = [vp, C.c_int]; L.rkfdBatchJoin.argtypes = [vp, vp]
     L.rkfdBatchTimeLaunches.argtypes = [vp, C.c_int]; L.rkfdBatchLaunchTiming.argtypes = [vp, vp, vp]
@@ -223,6 +228,39 @@ def _links_arrays(n, nl, nc, flags):
     """host arrays of a read-out over n instances: {name: array} of the quantities `flags` selects"""
     shapes = {"R": (n, nl, 3, 3), "p": (n, nl, 3), "v": (n, nl, 6), "com": (n, nc, 3), "comvel": (n, nc, 3)}
     return {k: np.empty(shapes[k]) for k, f in _LINKS_KEYS if flags & f}
+
+
+# per-instance reset (include/rkfd_hip.h: RKFD_RESET_*): slot values besides the rows 0 .. nslots-1 of the bank
+RESET_KEEP, RESET_SNAPSHOT = -1, -2
+
+
+def reset_slots(slots, n, device=None):
+    """the slot values of a reset over n instances, checked before any library call -> ("host", int32 array (n,)) or ("dev",
+    tensor).  A numpy int32 array (n,) is taken as it is; a numpy bool mask (n,) stands for RESET_SNAPSHOT where True and
+    RESET_KEEP where False; a contiguous torch int32 tensor (n,) on cuda:`device` is read in place (device=None: host forms only)."""
+    if isinstance(slots, np.ndarray):
+        if slots.shape != (n,):
+            raise ValueError(f"reset slots of shape {slots.shape}: expected ({n},)")
+        if slots.dtype == np.bool_:
+            return "host", np.where(slots, RESET_SNAPSHOT, RESET_KEEP).astype(np.int32)
+        if slots.dtype != np.int32:
+            raise TypeError(f"reset slots of dtype {slots.dtype}: expected int32 (slot values) or bool (a mask: True = RESET_SNAPSHOT)")
+        return "host", np.ascontiguousarray(slots)
+    if type(slots).__module__.split(".")[0] != "torch" or device is None:
+        raise TypeError(f"reset slots of type {type(slots).__name__}: expected a numpy int32 or bool array"
+                        + ("" if device is None else " or a torch int32 tensor"))
+    import torch
+    if not isinstance(slots, torch.Tensor):
+        raise TypeError(f"reset slots of type {type(slots).__name__}: expected a numpy int32 or bool array or a torch int32 tensor")
+    if tuple(slots.shape) != (n,):
+        raise ValueError(f"reset slots of shape {tuple(slots.shape)}: expected ({n},)")
+    if slots.dtype != torch.int32:
+        raise TypeError(f"reset slots of dtype {slots.dtype}: expected torch.int32")
+    if slots.device.type != "cuda" or slots.device.index != device:
+        raise ValueError(f"reset slots on {slots.device}: expected cuda:{device}")
+    if not slots.is_contiguous():
+        raise ValueError("reset slots: the tensor must be contiguous")
+    return "dev", slots
 
 
 # per-instance physical parameters (include/rkfd_hip.h: RKFD_PAR_*): the key of a name is its place here
@@ -414,6 +452,35 @@ class Batch:
     def restore(self, stream=None):
         """put the snapshot back, in stream order (no host traffic)"""
         self._chk(self._L.rkfdBatchRestore(self._b, C.c_void_p(stream or 0)))
+
+    def bank_reserve(self, nslots):
+        """rkfdBatchBankReserve: (re)allocate the bank of start states with nslots rows on the batch's device (contents undefined);
+        0 frees it.  Synchronous."""
+        self._synced(self._L.rkfdBatchBankReserve(self._b, int(nslots)))
+
+    def bank_size(self):
+        return self._L.rkfdBatchBankSize(self._b)
+
+    def bank_store(self, slot, first=0, count=1):
+        """rows slot .. slot+count-1 of the bank <- the live state of the instances first .. first+count-1 (after update_init, and
+        any steps, the rows hold consistent accelerations, pivots, anchors and forces).  Synchronous."""
+        self._synced(self._L.rkfdBatchBankStore(self._b, int(slot), int(first), int(count)))
+
+    def reset(self, slots, stream=None):
+        """per-instance reset ON THE DEVICE, in stream order (rkfdBatchReset): instance i gets bank row slots[i], keeps its state
+        (RESET_KEEP) or gets its own row of snapshot() (RESET_SNAPSHOT); any other value leaves it as it is and status() reports 5.
+        slots: a numpy int32 array (B,), copied before the call returns; a numpy bool mask (B,) - True: RESET_SNAPSHOT, False:
+        RESET_KEEP; or a contiguous torch int32 tensor (B,) on the batch's device - read in place, in order after `stream`
+        (default: torch.cuda.current_stream()), and kept referenced until join() or a synchronous accessor."""
+        kind, s = reset_slots(slots, self.B, self.device)
+        if kind == "host":
+            self._chk(self._L.rkfdBatchReset(self._b, _ptr(s), C.c_void_p(stream or 0)))
+            return
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(s.device).cuda_stream
+        self._chk(self._L.rkfdBatchResetDev(self._b, C.c_void_p(s.data_ptr()), C.c_void_p(stream or 0)))
+        self._ctrl_keep.append(s)      # read by a launch that may still be queued
 
     def set_split(self, nsplit):
         """rkfdBatchSetSplit: launch the batch as nsplit kernels on internal streams (tails overlap)"""
@@ -623,6 +690,19 @@ class Node:
 
     def status(self):
         return self._chk(self._L.rkfdNodeStatus(self._n))
+
+    def bank_reserve(self, nslots):
+        """Batch.bank_reserve on every device: the bank is replicated, like the model"""
+        self._chk(self._L.rkfdNodeBankReserve(self._n, int(nslots)))
+
+    def bank_store(self, slot, first=0, count=1):
+        """rows slot .. of EVERY device's bank <- the live state of the instances first .. first+count-1, GLOBAL indices"""
+        self._chk(self._L.rkfdNodeBankStore(self._n, int(slot), int(first), int(count)))
+
+    def reset(self, slots):
+        """Batch.reset over all instances: slots is a numpy int32 array or bool mask (total,), sharded like set_state"""
+        _, s = reset_slots(slots, self.total)
+        self._chk(self._L.rkfdNodeReset(self._n, _ptr(s)))
 
     def get_links(self, flags=LINKS_ALL):
         """Batch.update_links(flags) on every device's own thread and stream, then the results of ALL instances in instance

@@ -18,6 +18,7 @@
 #include "rkfd_device.h"
 #include "rkfd_devmodel_host.h"
 #include "readout/rkfd_links_host.h"   /* the task-space read-out (rkfd_capi_links.hip) */
+#include "reset/rkfd_reset_host.h"     /* the per-instance reset and its bank of start states (rkfd_capi_reset.hip) */
 #include "rkfd_device_src.inc"       /* the device headers as string literals (tools/embed_sources.py), for hipRTC */
 
 static thread_local char g_err[512] = "";
@@ -160,6 +161,9 @@ struct rkfdBatch {
    * a batch that never asks has none; par_gen counts the changes of the parameter table (the read-out keeps model-space rows of its own) */
   rkfdLinks *links;
   int par_gen;
+  /* rkfdBatchBankReserve / rkfdBatchReset: the bank of start states and the staging of the slot values (rkfd_capi_reset.hip), made by
+   * the first of those calls - a batch that never resets one instance alone has none */
+  rkfdReset *reset;
 };
 
 extern "C" const char *rkfdHipLastError(void){ return g_err; }
@@ -268,6 +272,7 @@ extern "C" void rkfdBatchDestroy(rkfdBatch *b)
   (void)hipFree( b->d_ctrl ); if( b->h_ctrl ) (void)hipHostFree( b->h_ctrl );
   (void)hipFree( b->d_par ); for( int k=0; k<RKFD_PAR_COUNT; k++ ) free( b->h_par[k] );
   rkfd_links_destroy( b->links );
+  rkfd_reset_destroy( b->reset );
   if( b->spec_mod ) (void)hipModuleUnload( b->spec_mod );
   (void)hipFree( b->d_err ); (void)hipFree( b->dblob ); (void)hipFree( b->dblob2 );
   rkfd_devmodel_free( &b->host ); rkfd_devmodel_free( &b->host2 );
@@ -1204,6 +1209,8 @@ extern "C" int rkfdBatchStatus(rkfdBatch *b, void *stream)
   if( e == 3 ) SETERR( "the %s plugin's QP ran out of iterations (256) or of basis history (64) in at least one instance", b->dm.vol_np > 0 ? "Volume" : "Vert" );
   if( e == 4 ) SETERR( "Volume plugin: a rigid pair the device cannot clip (a shape that is not convex, or more than 64 faces together) came into "
                        "contact in at least one instance; it was left without a contact force" );
+  if( e == 5 ) SETERR( "rkfdBatchReset: at least one slot value named no row - not RKFD_RESET_KEEP, not a row of the bank (%d reserved), or "
+                       "RKFD_RESET_SNAPSHOT without a snapshot; those instances were left as they were", rkfd_reset_size( b->reset ) );
   if( e != 0 ){
     /* the condition is reported once: the flag is cleared, so a later status describes what happened after this call */
     const int zero = 0;
@@ -1280,6 +1287,112 @@ extern "C" int rkfdBatchRestore(rkfdBatch *b, void *stream)
   }
   b->pending = 1;
   return 0;
+}
+
+/* ---- per-instance reset from a bank of start states ----------------------------------------------------------- */
+/* the bank's object is made by the first call that needs it; it allocates nothing on the device by itself */
+static int reset_object(rkfdBatch *b, const char *who)
+{
+  if( b->reset ) return 0;
+  char err[400] = "";
+  b->reset = rkfd_reset_create( b->batch, b->ndof, b->nlink, b->ncand, err, sizeof(err) );
+  if( !b->reset ){ SETERR( "%s: %s", who, err ); return -1; }
+  return 0;
+}
+extern "C" int rkfdBatchBankSize(const rkfdBatch *b){ return b ? rkfd_reset_size( b->reset ) : -1; }
+extern "C" int rkfdBatchBankReserve(rkfdBatch *b, int nslots)
+{
+  if( !b ){ SETERR( "rkfdBatchBankReserve: null batch" ); return -1; }
+  if( nslots < 0 ){ SETERR( "rkfdBatchBankReserve: nslots must be >= 0 (got %d)", nslots ); return -1; }
+  if( nslots == 0 && !b->reset ) return 0;
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  /* a reset still queued may read the rows that go */
+  if( sync_streams( b ) < 0 ) return -1;
+  HIPCHK( hipDeviceSynchronize(), -1 );
+  if( reset_object( b, "rkfdBatchBankReserve" ) < 0 ) return -1;
+  char err[400] = "";
+  if( rkfd_reset_reserve( b->reset, nslots, err, sizeof(err) ) < 0 ){ SETERR( "rkfdBatchBankReserve: %s", err ); return -1; }
+  return 0;
+}
+extern "C" int rkfdBatchBankStore(rkfdBatch *b, int slot, int first, int count)
+{
+  if( !b ){ SETERR( "rkfdBatchBankStore: null batch" ); return -1; }
+  if( !b->reset || rkfd_reset_size( b->reset ) == 0 ){ SETERR( "rkfdBatchBankStore: no bank has been reserved (rkfdBatchBankReserve)" ); return -1; }
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  if( sync_streams( b ) < 0 ) return -1;
+  HIPCHK( hipDeviceSynchronize(), -1 );
+  char err[400] = "";
+  if( rkfd_reset_store( b->reset, &b->st, slot, first, count, err, sizeof(err) ) < 0 ){ SETERR( "rkfdBatchBankStore: %s", err ); return -1; }
+  return 0;
+}
+/* slots_dev: the caller's device array, or NULL: the batch's own copy, which every part first brings over from the pinned staging
+ * (as ctrl_upload does for a control schedule).  Under split launches every part resets itself on its own stream, in order with
+ * its steps, as rkfdBatchRestore does. */
+static int reset_launch(rkfdBatch *b, const int *slots_dev, void *stream, const char *who)
+{
+  char err[400] = "";
+  const bool upload = slots_dev == NULL;
+  if( upload ) slots_dev = rkfd_reset_dev_slots( b->reset );
+  const rkfdDevState *snap = b->has_snap ? &b->snap : NULL;
+  b->last_stream = (hipStream_t)stream; b->launched = 1;
+  if( b->nsplit <= 1 ){
+    if( ( upload && rkfd_reset_upload( b->reset, 0, b->batch, 0, stream, err, sizeof(err) ) < 0 ) ||
+        rkfd_reset_launch( b->reset, &b->st, snap, slots_dev, 0, b->batch, b->d_err, stream, err, sizeof(err) ) < 0 ){ SETERR( "%s: %s", who, err ); return -1; }
+    return 0;
+  }
+  HIPCHK( hipEventRecord( b->fork, (hipStream_t)stream ), -1 );
+  for( int k=0; k<b->nsplit; k++ ){
+    HIPCHK( hipStreamWaitEvent( b->sub[k], b->fork, 0 ), -1 );
+    const int lo = (int)( (long long)b->batch*k/b->nsplit ), hi = (int)( (long long)b->batch*( k+1 )/b->nsplit );
+    if( hi > lo && ( ( upload && rkfd_reset_upload( b->reset, lo, hi, k, b->sub[k], err, sizeof(err) ) < 0 ) ||
+                     rkfd_reset_launch( b->reset, &b->st, snap, slots_dev, lo, hi, b->d_err, b->sub[k], err, sizeof(err) ) < 0 ) ){ SETERR( "%s: %s", who, err ); return -1; }
+    HIPCHK( hipEventRecord( b->done[k], b->sub[k] ), -1 );
+  }
+  b->pending = 1;
+  return 0;
+}
+/* the first half of rkfdBatchReset: the host array into the batch's pinned staging; nothing on the device has changed when it fails
+ * (the node level stages every shard before any of them launches) */
+static int reset_stage(rkfdBatch *b, const int *slots, const char *who)
+{
+  if( !b || !slots ){ SETERR( "%s: %s", who, !b ? "null batch" : "null slots" ); return -1; }
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  if( reset_object( b, who ) < 0 ) return -1;
+  char err[400] = "";
+  if( rkfd_reset_stage( b->reset, slots, err, sizeof(err) ) < 0 ){ SETERR( "%s: %s", who, err ); return -1; }
+  return 0;
+}
+extern "C" int rkfdBatchReset(rkfdBatch *b, const int *slots, void *stream)
+{
+  if( reset_stage( b, slots, "rkfdBatchReset" ) < 0 ) return -1;
+  return reset_launch( b, NULL, stream, "rkfdBatchReset" );
+}
+/* the node level's route through the host (rkfdNodeBankStore): packed rows of live instances out of a batch, and into the bank of
+ * another; synchronous and ordered after the batch's launches */
+static int bank_rows_get(rkfdBatch *b, int first, int count, void *buf)
+{
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  if( sync_streams( b ) < 0 ) return -1;
+  HIPCHK( hipDeviceSynchronize(), -1 );
+  char err[400] = "";
+  if( rkfd_reset_rows_get( b->reset, &b->st, first, count, buf, err, sizeof(err) ) < 0 ){ SETERR( "rkfdNodeBankStore: %s", err ); return -1; }
+  return 0;
+}
+static int bank_rows_put(rkfdBatch *b, int slot, int count, const void *buf)
+{
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  if( sync_streams( b ) < 0 ) return -1;
+  HIPCHK( hipDeviceSynchronize(), -1 );
+  char err[400] = "";
+  if( rkfd_reset_rows_put( b->reset, slot, count, buf, err, sizeof(err) ) < 0 ){ SETERR( "rkfdNodeBankStore: %s", err ); return -1; }
+  return 0;
+}
+extern "C" int rkfdBatchResetDev(rkfdBatch *b, const int *slots_dev, void *stream)
+{
+  if( !b || !slots_dev ){ SETERR( "rkfdBatchResetDev: %s", !b ? "null batch" : "null slots" ); return -1; }
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  if( reset_object( b, "rkfdBatchResetDev" ) < 0 ) return -1;
+  return reset_launch( b, slots_dev, stream, "rkfdBatchResetDev" );
 }
 
 /* ---- task-space read-out: link poses, velocities and chain COM on the device ---------------------------------- */

@@ -48,7 +48,7 @@ static const rkfdRccl *rccl_api(void)
   return state == 1 ? &api : NULL;
 }
 
-enum { NODE_CMD_NONE = 0, NODE_CMD_INIT, NODE_CMD_UPDATE, NODE_CMD_SPECIALIZE, NODE_CMD_SPLIT, NODE_CMD_STEPS_PER_LAUNCH, NODE_CMD_TUNE, NODE_CMD_STATUS, NODE_CMD_SNAPSHOT, NODE_CMD_RESTORE, NODE_CMD_PACK, NODE_CMD_UPDATE_CTRL, NODE_CMD_LINKS, NODE_CMD_QUIT };
+enum { NODE_CMD_NONE = 0, NODE_CMD_INIT, NODE_CMD_UPDATE, NODE_CMD_SPECIALIZE, NODE_CMD_SPLIT, NODE_CMD_STEPS_PER_LAUNCH, NODE_CMD_TUNE, NODE_CMD_STATUS, NODE_CMD_SNAPSHOT, NODE_CMD_RESTORE, NODE_CMD_PACK, NODE_CMD_UPDATE_CTRL, NODE_CMD_LINKS, NODE_CMD_RESET, NODE_CMD_QUIT };
 
 struct rkfdNode;
 struct rkfdNodeWorker {
@@ -84,6 +84,7 @@ static int node_run_on(rkfdNode *n, int k, int cmd, int arg)
   case NODE_CMD_UPDATE:     return rkfdBatchUpdate( b, arg, n->st[k] );
   case NODE_CMD_UPDATE_CTRL: return rkfdBatchUpdateControlled( b, arg, n->ctrl + (size_t)n->lo[k]*arg*n->nlink, n->st[k] );
   case NODE_CMD_LINKS:      return rkfdBatchUpdateLinks( b, arg, n->st[k] );
+  case NODE_CMD_RESET:      return reset_launch( b, NULL, n->st[k], "rkfdNodeReset" );      /* (rkfdNodeReset has staged the shard's slot values) */
   case NODE_CMD_SPECIALIZE: return rkfdBatchSpecialize( b );
   case NODE_CMD_SPLIT:      return rkfdBatchSetSplit( b, arg );
   case NODE_CMD_STEPS_PER_LAUNCH: return rkfdBatchSetStepsPerLaunch( b, arg );
@@ -293,6 +294,42 @@ extern "C" int rkfdNodeUpdateControlled(rkfdNode *n, int nsteps, const double *u
   const int r = node_all( n, NODE_CMD_UPDATE_CTRL, nsteps );
   n->ctrl = NULL;
   return r;
+}
+
+/* ---- per-instance reset over all instances: the bank is replicated like the model, the slot values are sharded like the state ---- */
+extern "C" int rkfdNodeBankReserve(rkfdNode *n, int nslots)
+{
+  if( !n ){ SETERR( "rkfdNodeBankReserve: null node" ); return -1; }
+  if( nslots < 0 ){ SETERR( "rkfdNodeBankReserve: nslots must be >= 0 (got %d)", nslots ); return -1; }
+  for( int k=0; k<n->ndev; k++ ) if( rkfdBatchBankReserve( n->b[k], nslots ) < 0 ) return -1;
+  return 0;
+}
+/* rows slot .. slot+count-1 of EVERY device's bank <- the live state of the instances first .. first+count-1 (global indices): read
+ * from the shards that own them, through the host */
+extern "C" int rkfdNodeBankStore(rkfdNode *n, int slot, int first, int count)
+{
+  if( !n ){ SETERR( "rkfdNodeBankStore: null node" ); return -1; }
+  if( count < 1 || first < 0 || (long long)first + count > n->total ){ SETERR( "rkfdNodeBankStore: instances %d .. %d are not within the %d of the node", first, first+count-1, n->total ); return -1; }
+  for( int k=0; k<n->ndev; k++ ){
+    const int have = rkfdBatchBankSize( n->b[k] );
+    if( slot < 0 || (long long)slot + count > have ){ SETERR( "rkfdNodeBankStore: rows %d .. %d are not within the bank of %d (rkfdNodeBankReserve)", slot, slot+count-1, have ); return -1; }
+  }
+  for( int k=0; k<n->ndev; k++ ){
+    const int lo = first > n->lo[k] ? first : n->lo[k], hi = first + count < n->hi[k] ? first + count : n->hi[k];
+    if( hi <= lo ) continue;
+    std::vector<char> buf( rkfd_reset_row_bytes( n->b[k]->reset, hi-lo ) + 8 );
+    if( bank_rows_get( n->b[k], lo - n->lo[k], hi-lo, buf.data() ) < 0 ) return -1;
+    for( int j=0; j<n->ndev; j++ ) if( bank_rows_put( n->b[j], slot + ( lo-first ), hi-lo, buf.data() ) < 0 ) return -1;
+  }
+  return 0;
+}
+/* slots[total] on the host, sharded like rkfdNodeSetState: every shard's block goes into its batch's pinned staging first - a
+ * refusal there leaves every device as it was -, then every device's own thread issues its reset on its own stream */
+extern "C" int rkfdNodeReset(rkfdNode *n, const int *slots)
+{
+  if( !n || !slots ){ SETERR( "rkfdNodeReset: %s", !n ? "null node" : "null slots" ); return -1; }
+  for( int k=0; k<n->ndev; k++ ) if( reset_stage( n->b[k], slots + n->lo[k], "rkfdNodeReset" ) < 0 ) return -1;
+  return node_all( n, NODE_CMD_RESET, 0 );
 }
 
 /* the task-space read-out over all instances: rkfdBatchUpdateLinks on every device's own thread and stream, then the host arrays
