@@ -289,6 +289,43 @@ const double *rkfdBatchDevLinkVel(rkfdBatch *b);
 const double *rkfdBatchDevCom(rkfdBatch *b);
 const double *rkfdBatchDevComVel(rkfdBatch *b);
 
+/* ---- task-space Jacobians: the map from the joint rates to the velocities the read-out reports, computed ON THE DEVICE ----
+ * What lies between a task-space cost and a joint command (operational-space control, whole-body QPs, a balance controller on the
+ * centre of mass, J' f for a desired contact force, the gradient of a task-space cost).  A SITE is a model link plus a point in
+ * that link's frame.  One kernel launch (rkfd_jac_kernel, a kernel of its own: the step kernels and the read-out are untouched)
+ * computes, for every instance,
+ *   J    [batch][nsite][6][ndof]   world frame: rows 0-2 times vel = velocity of the site point, rows 3-5 times vel = angular
+ *                                  velocity of the site's link - with R, ( v, w ) of the read-out at the same state:
+ *                                  J[s][0:3] vel = R ( v + w x point ),  J[s][3:6] vel = R w
+ *   Jcom [batch][nchain][3][ndof]  world frame: Jcom[c] vel = comvel[c] of the read-out (the instance's own masses and centres of
+ *                                  mass when the batch carries a table of per-instance parameters; zeros for a chain without mass)
+ * `vel` is the packed rate vector of rkfdBatchSetState / GetState, so the columns are derivatives with respect to the RATES
+ * (DEVIATIONS.md items 1-2): the scalar rate of a revolute / prismatic joint about / along local z, ( v, w ) of a float or breakable
+ * float joint and w of a spherical joint in the joint-origin frame - not derivatives with respect to the angle-axis coordinates.
+ * A breakable float joint contributes its six columns whether it has broken or not, as in the read-out.  Columns of coordinates that
+ * do not move the site (other chains, joints that are no ancestors of its link) are exactly 0.0.  J is the exact linear map of the
+ * model's own velocity recursion (readout/rkfd_jac.h), not axis x lever arm on composed world frames.
+ * A batch that never calls these allocates nothing and launches nothing; snapshot / restore / reset do not touch the results
+ * (derived data). */
+enum { RKFD_JAC_SITES = 1, RKFD_JAC_COM = 2 };
+/* the sites of the following launches: link[nsite] model links, point[nsite][3] in the link's frame or NULL for the link origins.
+ * Synchronous (waits for a Jacobian launch in flight); nsite = 0 clears the sites; the result buffer is reallocated only when
+ * nsite changes.  -1 with a message, the previous sites staying in place, for a link outside [0, nlink), a point that is not finite
+ * or nsite > 64 */
+int rkfdBatchSetJacobianSites(rkfdBatch *b, int nsite, const int *link, const double *point);
+int rkfdBatchJacobianSiteNum(const rkfdBatch *b);
+/* computes the selected Jacobians from the live state, in stream order after everything the batch has launched (joins the internal
+ * split streams onto `stream` first, as rkfdBatchUpdateLinks does); asynchronous; changes no state.  -1 with a message for
+ * RKFD_JAC_SITES without sites, flags 0 or unknown bits */
+int rkfdBatchUpdateJacobians(rkfdBatch *b, int flags, void *stream);
+/* host copies of the last rkfdBatchUpdateJacobians (waits for it); either pointer may be NULL; -1 with a message when a requested
+ * one was not part of the last launch, none was made, or the sites were replaced since */
+int rkfdBatchGetJacobians(rkfdBatch *b, double *J, double *Jcom);
+/* device pointers to the same buffers (owned by the batch, allocated at the first launch that needs them, stable while nsite stays;
+ * NULL before, and for J after nsite changed until the next launch) */
+const double *rkfdBatchDevJacobian(rkfdBatch *b);
+const double *rkfdBatchDevComJacobian(rkfdBatch *b);
+
 /* ---- the node level: all the GPUs of one node from ONE process, host code in C -------------------------------------
  * SURVEY 8e / north star: "independent MPC-style rollouts shard embarrassingly across the 8 GPUs of one node with an
  * RCCL-over-xGMI gather of final states only".  The instances of a batch are independent (one rkFD never references another),
@@ -342,6 +379,11 @@ int rkfdNodeReset(rkfdNode *n, const int *slots);
 /* rkfdBatchUpdateLinks( flags ) on every device's own thread and stream, then host arrays over ALL instances in instance order
  * (shapes as rkfdBatchGetLinks with batch = total; pointers of quantities `flags` does not select must be NULL) */
 int rkfdNodeGetLinks(rkfdNode *n, int flags, double *R, double *p, double *v, double *com, double *comvel);
+/* rkfdBatchSetJacobianSites on every device (the sites are replicated, like the model; nothing is changed on any device when the
+ * list is refused); rkfdBatchUpdateJacobians( flags ) on every device's own thread and stream, then host arrays over ALL instances
+ * in instance order (shapes as rkfdBatchGetJacobians with batch = total; the pointer of a quantity `flags` does not select must be NULL) */
+int rkfdNodeSetJacobianSites(rkfdNode *n, int nsite, const int *link, const double *point);
+int rkfdNodeGetJacobians(rkfdNode *n, int flags, double *J, double *Jcom);
 /* one ncclAllGather of the final {dis, vel}: afterwards every device holds all `total` final states (rkfdNodeGatherDev: on
  * device k, [ndev][mx][2 ndof] doubles - block j = shard j's instances, dis | vel per instance, padded to the largest shard mx),
  * and dis / vel ([total][ndof], either may be NULL) receive them on the host in instance order */

@@ -128,6 +128,12 @@ def lib():
     for f in ("rkfdBatchDevLinkAtt", "rkfdBatchDevLinkPos", "rkfdBatchDevLinkVel", "rkfdBatchDevCom", "rkfdBatchDevComVel"):
         getattr(L, f).argtypes = [vp]
         getattr(L, f).restype = vp
+    L.rkfdBatchSetJacobianSites.argtypes = [vp, C.c_int, vp, vp]; L.rkfdBatchJacobianSiteNum.argtypes = [vp]
+    L.rkfdBatchUpdateJacobians.argtypes = [vp, C.c_int, vp]; L.rkfdBatchGetJacobians.argtypes = [vp, vp, vp]
+    L.rkfdNodeSetJacobianSites.argtypes = [vp, C.c_int, vp, vp]; L.rkfdNodeGetJacobians.argtypes = [vp, C.c_int, vp, vp]
+    for f in ("rkfdBatchDevJacobian", "rkfdBatchDevComJacobian"):
+        getattr(L, f).argtypes = [vp]
+        getattr(L, f).restype = vp
     L.rkfdNodeCreate.argtypes = [C.POINTER(RkfdModel), C.c_int, C.c_int, C.c_int, vp]; L.rkfdNodeCreate.restype = vp
     L.rkfdNodeDestroy.argtypes = [vp]
     for f in ("rkfdNodeDevices", "rkfdNodeSize", "rkfdNodeSpecialize", "rkfdNodeUpdateInit", "rkfdNodeSnapshot", "rkfdNodeRestore", "rkfdNodeStatus"):
@@ -230,6 +236,28 @@ def _links_arrays(n, nl, nc, flags):
     return {k: np.empty(shapes[k]) for k, f in _LINKS_KEYS if flags & f}
 
 
+# task-space Jacobians (include/rkfd_hip.h: RKFD_JAC_*): what update_jacobians computes and get_jacobians returns
+JAC_SITES, JAC_COM = 1, 2
+JAC_ALL = JAC_SITES | JAC_COM
+_JAC_KEYS = (("J", JAC_SITES), ("Jcom", JAC_COM))
+
+
+def _jac_sites(links, points):
+    """(nsite, int32 links, float64 points (nsite, 3) or None) of a list of sites, shapes checked before any library call"""
+    links = np.ascontiguousarray(np.asarray(links, dtype=np.int32).reshape(-1))
+    if points is not None:
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        if points.shape != (links.size, 3):
+            raise ValueError(f"site points of shape {points.shape}: expected ({links.size}, 3)")
+    return links.size, links, points
+
+
+def _jac_arrays(n, ns, nc, nd, flags):
+    """host arrays of the Jacobians over n instances: {name: array} of the quantities `flags` selects"""
+    shapes = {"J": (n, ns, 6, nd), "Jcom": (n, nc, 3, nd)}
+    return {k: np.empty(shapes[k]) for k, f in _JAC_KEYS if flags & f}
+
+
 # per-instance reset (include/rkfd_hip.h: RKFD_RESET_*): slot values besides the rows 0 .. nslots-1 of the bank
 RESET_KEEP, RESET_SNAPSHOT = -1, -2
 
@@ -289,6 +317,7 @@ class Batch:
         self.B, self.ndof, self.nlink, self.ncand = batch, m.ndof, m.nlink, m.ncand
         self.nchain = m.nchain
         self._links_flags = 0          # what the last update_links() computed
+        self._jac_flags = 0            # what the last update_jacobians() computed, of the present sites
         self.device = device
         self._ctrl_keep = []           # device schedules of update_controlled() the launches issued since the last join / sync read
         self._owned = _handle is None
@@ -552,6 +581,49 @@ class Batch:
         self._chk(self._L.rkfdBatchGetLinks(self._b, *[_ptr(out.get(k)) for k, _ in _LINKS_KEYS]))
         return out
 
+    def set_jacobian_sites(self, links, points=None):
+        """the sites of the following update_jacobians(): model links (nsite,) and points (nsite, 3) in the links' frames (None:
+        the link origins); an empty list clears them.  Synchronous; a refused list leaves the previous sites in place."""
+        ns, links, points = _jac_sites(links, points)
+        self._chk(self._L.rkfdBatchSetJacobianSites(self._b, ns, _ptr(links), _ptr(points)))
+        self._jac_flags &= ~JAC_SITES
+
+    @property
+    def nsite(self):
+        return self._L.rkfdBatchJacobianSiteNum(self._b)
+
+    def update_jacobians(self, flags=JAC_ALL, stream=None):
+        """task-space Jacobians ON THE DEVICE from the live state: J (JAC_SITES) maps the packed joint RATES to the world velocity
+        of every site point and the world angular velocity of its link, Jcom (JAC_COM) to the velocity of every chain's centre of
+        mass.  One kernel launch in stream order after everything the batch has launched (no host wait, no state changed);
+        get_jacobians() / jacobian_tensors() hand the results out."""
+        self._chk(self._L.rkfdBatchUpdateJacobians(self._b, int(flags), stream))
+        self._jac_flags = int(flags)
+
+    def get_jacobians(self):
+        """host copies of the last update_jacobians(): a dict with (of what its flags selected) J [B, nsite, 6, ndof] and
+        Jcom [B, nc, 3, ndof], world frame, columns in the order of the packed rate vector"""
+        if not self._jac_flags:
+            raise RkfdError("get_jacobians: no Jacobians have been computed (update_jacobians)")
+        out = _jac_arrays(self.B, self.nsite, self.nchain, self.ndof, self._jac_flags)
+        self._chk(self._L.rkfdBatchGetJacobians(self._b, *[_ptr(out.get(k)) for k, _ in _JAC_KEYS]))
+        return out
+
+    def jacobian_ptrs(self):
+        """device addresses of J and Jcom (None for a buffer no update_jacobians() has needed yet; J's moves when nsite changes)"""
+        return (self._L.rkfdBatchDevJacobian(self._b), self._L.rkfdBatchDevComJacobian(self._b))
+
+    def jacobian_tensors(self):
+        """the Jacobians' buffers as a dict of zero-copy float64 torch views, J [B, nsite, 6, ndof] and Jcom [B, nc, 3, ndof]
+        (None where no update_jacobians() has needed the buffer yet)"""
+        import torch
+
+        class _View:
+            def __init__(self, ptr, shape):
+                self.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(int(ptr), False), version=2, strides=None)
+        shapes = ((self.B, self.nsite, 6, self.ndof), (self.B, self.nchain, 3, self.ndof))
+        return {k: torch.as_tensor(_View(p, sh), device="cuda") if p else None for (k, _), p, sh in zip(_JAC_KEYS, self.jacobian_ptrs(), shapes)}
+
     def dev_tensors(self, links=False):
         """torch tensors ALIASING the live device state [B, ndof] (dis, vel, acc): zero-copy views
         for consumers on the device, e.g. the RCCL all-gather of final states.  links=True: the buffers of the task-space
@@ -709,6 +781,19 @@ class Node:
         order, as Batch.get_links() returns them"""
         out = _links_arrays(self.total, self.nlink, self.nchain, int(flags))
         self._chk(self._L.rkfdNodeGetLinks(self._n, int(flags), *[_ptr(out.get(k)) for k, _ in _LINKS_KEYS]))
+        return out
+
+    def set_jacobian_sites(self, links, points=None):
+        """Batch.set_jacobian_sites on every device: the sites are replicated, like the model"""
+        ns, links, points = _jac_sites(links, points)
+        self._chk(self._L.rkfdNodeSetJacobianSites(self._n, ns, _ptr(links), _ptr(points)))
+
+    def get_jacobians(self, flags=JAC_ALL):
+        """Batch.update_jacobians(flags) on every device's own thread and stream, then the results of ALL instances in instance
+        order, as Batch.get_jacobians() returns them"""
+        ns = max(self._L.rkfdBatchJacobianSiteNum(self._L.rkfdNodeBatch(self._n, 0)), 0)
+        out = _jac_arrays(self.total, ns, self.nchain, self.ndof, int(flags))
+        self._chk(self._L.rkfdNodeGetJacobians(self._n, int(flags), *[_ptr(out.get(k)) for k, _ in _JAC_KEYS]))
         return out
 
     def gather(self):

@@ -18,6 +18,7 @@
 #include "rkfd_device.h"
 #include "rkfd_devmodel_host.h"
 #include "readout/rkfd_links_host.h"   /* the task-space read-out (rkfd_capi_links.hip) */
+#include "readout/rkfd_jac_host.h"     /* the task-space Jacobians (rkfd_capi_jac.hip) */
 #include "reset/rkfd_reset_host.h"     /* the per-instance reset and its bank of start states (rkfd_capi_reset.hip) */
 #include "rkfd_device_src.inc"       /* the device headers as string literals (tools/embed_sources.py), for hipRTC */
 
@@ -161,6 +162,9 @@ struct rkfdBatch {
    * a batch that never asks has none; par_gen counts the changes of the parameter table (the read-out keeps model-space rows of its own) */
   rkfdLinks *links;
   int par_gen;
+  /* rkfdBatchSetJacobianSites / UpdateJacobians: the Jacobians' tables, sites and result buffers (rkfd_capi_jac.hip), made by the
+   * first of those calls - a batch that never asks has none */
+  rkfdJac *jac;
   /* rkfdBatchBankReserve / rkfdBatchReset: the bank of start states and the staging of the slot values (rkfd_capi_reset.hip), made by
    * the first of those calls - a batch that never resets one instance alone has none */
   rkfdReset *reset;
@@ -272,6 +276,7 @@ extern "C" void rkfdBatchDestroy(rkfdBatch *b)
   (void)hipFree( b->d_ctrl ); if( b->h_ctrl ) (void)hipHostFree( b->h_ctrl );
   (void)hipFree( b->d_par ); for( int k=0; k<RKFD_PAR_COUNT; k++ ) free( b->h_par[k] );
   rkfd_links_destroy( b->links );
+  rkfd_jac_destroy( b->jac );
   rkfd_reset_destroy( b->reset );
   if( b->spec_mod ) (void)hipModuleUnload( b->spec_mod );
   (void)hipFree( b->d_err ); (void)hipFree( b->dblob ); (void)hipFree( b->dblob2 );
@@ -1436,5 +1441,62 @@ extern "C" const double *rkfdBatchDevLinkPos(rkfdBatch *b){ return b ? rkfd_link
 extern "C" const double *rkfdBatchDevLinkVel(rkfdBatch *b){ return b ? rkfd_links_dev( b->links, 2 ) : NULL; }
 extern "C" const double *rkfdBatchDevCom(rkfdBatch *b){ return b ? rkfd_links_dev( b->links, 3 ) : NULL; }
 extern "C" const double *rkfdBatchDevComVel(rkfdBatch *b){ return b ? rkfd_links_dev( b->links, 4 ) : NULL; }
+
+/* ---- task-space Jacobians: site and centre-of-mass Jacobians on the device ------------------------------------ */
+static int jac_object(rkfdBatch *b, const char *who)
+{
+  if( b->jac ) return 0;
+  char err[400] = "";
+  b->jac = rkfd_jac_create( b->model_for_w2, b->batch, err, sizeof(err) );
+  if( !b->jac ){ SETERR( "%s: %s", who, err ); return -1; }
+  return 0;
+}
+extern "C" int rkfdBatchSetJacobianSites(rkfdBatch *b, int nsite, const int *link, const double *point)
+{
+  if( !b ){ SETERR( "rkfdBatchSetJacobianSites: null batch" ); return -1; }
+  char err[400] = "";
+  /* (refused before anything is made or touched: the previous sites stay) */
+  if( rkfd_jac_check_sites( b->nlink, nsite, link, point, err, sizeof(err) ) < 0 ){ SETERR( "rkfdBatchSetJacobianSites: %s", err ); return -1; }
+  if( !b->jac && nsite == 0 ) return 0;
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  if( jac_object( b, "rkfdBatchSetJacobianSites" ) < 0 ) return -1;
+  if( rkfd_jac_set_sites( b->jac, nsite, link, point, err, sizeof(err) ) < 0 ){ SETERR( "rkfdBatchSetJacobianSites: %s", err ); return -1; }
+  return 0;
+}
+extern "C" int rkfdBatchJacobianSiteNum(const rkfdBatch *b){ return b ? rkfd_jac_nsite( b->jac ) : -1; }
+/* One launch of rkfd_jac_kernel in stream order after everything the batch has launched: the internal split streams are joined
+ * onto `stream` first (as rkfdBatchJoin does), no host wait.  It reads dis and writes the Jacobians' own buffers only. */
+extern "C" int rkfdBatchUpdateJacobians(rkfdBatch *b, int flags, void *stream)
+{
+  if( !b ){ SETERR( "rkfdBatchUpdateJacobians: null batch" ); return -1; }
+  if( flags <= 0 || ( flags & ~( RKFD_JAC_SITES | RKFD_JAC_COM ) ) ){ SETERR( "rkfdBatchUpdateJacobians: flags must be a combination of RKFD_JAC_SITES and RKFD_JAC_COM (got %d)", flags ); return -1; }
+  if( ( flags & RKFD_JAC_SITES ) && rkfd_jac_nsite( b->jac ) == 0 ){ SETERR( "rkfdBatchUpdateJacobians: RKFD_JAC_SITES without sites (rkfdBatchSetJacobianSites)" ); return -1; }
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  if( jac_object( b, "rkfdBatchUpdateJacobians" ) < 0 ) return -1;
+  if( join_streams( b, (hipStream_t)stream ) < 0 ) return -1;
+  b->last_stream = (hipStream_t)stream; b->launched = 1;
+  char err[400] = "";
+  if( rkfd_jac_launch( b->jac, b->st.dis, flags, b->d_par ? b->h_par[RKFD_PAR_MASS] : NULL, b->d_par ? b->h_par[RKFD_PAR_COM] : NULL,
+                       b->par_gen, stream, err, sizeof(err) ) < 0 ){ SETERR( "rkfdBatchUpdateJacobians: %s", err ); return -1; }
+  return 0;
+}
+extern "C" int rkfdBatchGetJacobians(rkfdBatch *b, double *J, double *Jcom)
+{
+  if( !b ){ SETERR( "rkfdBatchGetJacobians: null batch" ); return -1; }
+  const int have = rkfd_jac_flags( b->jac );
+  if( ( J && !( have & RKFD_JAC_SITES ) ) || ( Jcom && !( have & RKFD_JAC_COM ) ) ){
+    if( !have ) SETERR( "rkfdBatchGetJacobians: no Jacobians have been computed (rkfdBatchUpdateJacobians)" );
+    else SETERR( "rkfdBatchGetJacobians: the last rkfdBatchUpdateJacobians (flags %d) did not compute %s", have,
+                 ( J && !( have & RKFD_JAC_SITES ) ) ? "the site Jacobians of the present sites (RKFD_JAC_SITES)" : "the centre-of-mass Jacobians (RKFD_JAC_COM)" );
+    return -1;
+  }
+  if( !J && !Jcom ) return 0;
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  char err[400] = "";
+  if( rkfd_jac_get( b->jac, J, Jcom, err, sizeof(err) ) < 0 ){ SETERR( "rkfdBatchGetJacobians: %s", err ); return -1; }
+  return 0;
+}
+extern "C" const double *rkfdBatchDevJacobian(rkfdBatch *b){ return b ? rkfd_jac_dev( b->jac, 0 ) : NULL; }
+extern "C" const double *rkfdBatchDevComJacobian(rkfdBatch *b){ return b ? rkfd_jac_dev( b->jac, 1 ) : NULL; }
 
 #include "rkfd_capi_node.inc"      /* the node level: one host thread + stream per device, one RCCL all-gather of final states */
