@@ -45,7 +45,7 @@ int rkfdBatchDof(const rkfdBatch *b);
 
 /* The Set / Get accessors below are SYNCHRONOUS and ordered after the batch's launches: each waits for the batch's internal
  * (split) streams and for the stream its LAST launch was given (rkfdBatchUpdateInit / Update / UpdateControlled[Dev] / Eval /
- * Restore / Reset[Dev] / UpdateLinks) before it copies - also when that stream was made with hipStreamNonBlocking, which the null stream of the
+ * Restore / Reset[Dev] / UpdateLinks / UpdateJacobians / UpdateDynamics) before it copies - also when that stream was made with hipStreamNonBlocking, which the null stream of the
  * copies is not ordered against.  A value set is seen by every launch made after the call returns; a value read is what the
  * launches made before the call left.  Launches a caller spread over FURTHER streams of its own must be joined by the caller first
  * (rkfdBatchStatus on each, or its own events): only the stream of the last launch is known to the batch.  That stream must
@@ -326,6 +326,47 @@ int rkfdBatchGetJacobians(rkfdBatch *b, double *J, double *Jcom);
 const double *rkfdBatchDevJacobian(rkfdBatch *b);
 const double *rkfdBatchDevComJacobian(rkfdBatch *b);
 
+/* ---- joint-space dynamics: the other half of the equation of motion, computed ON THE DEVICE ----------------------------------
+ *   M(q) qdd + h(q, qd) = tau + J_c' f
+ * What an operational-space controller ( ( J M^-1 J' )^-1 ), a whole-body QP (M and h in its equality constraint), gravity
+ * compensation ( g(q) ) and an inverse-dynamics feed-forward ( M qdd_des + h ) need beside the Jacobians.  One kernel launch
+ * (rkfd_dyn_kernel, a kernel of its own: the step kernels, the read-out and the Jacobians are untouched) computes, for every
+ * instance from its live dis / vel,
+ *   M [batch][ndof][ndof]  the joint-space inertia matrix with respect to the packed RATES - the `vel` vector of rkfdBatchSetState,
+ *                          the coordinates of the columns of J (DEVIATIONS.md items 1-2), not derivatives of the angle-axis
+ *                          coordinates -: 0.5 vel' M vel is the kinetic energy of the velocities the read-out reports.  Exactly
+ *                          symmetric (M[i][j] and M[j][i] are the same bits); blocks between coordinates of different chains, and
+ *                          between coordinates where neither owner is an ancestor of the other, are exactly 0.0
+ *   h [batch][ndof]        the bias force rnea( q, qd, 0 ): Coriolis and centrifugal terms plus gravity (RKFD_G along -z, as in the
+ *                          step); the sign is such that M qdd + h is the generalised force on the coordinates
+ *   g [batch][ndof]        gravity alone, rnea( q, 0, 0 )
+ * Generalised forces: a revolute / prismatic joint takes the scalar about / along local z, a float or breakable float joint (force,
+ * moment about the link origin) on the joint-origin axes, a spherical joint the moment on those axes.  A breakable float joint is a
+ * float joint here whether it has broken or not, as in the read-out and the Jacobians: a caller who wants the intact system drops its
+ * six rows and columns (DEVIATIONS.md).  NOT part of h: joint friction (it depends on the pivot state), actuator torques, and contact
+ * forces - the caller has J and rkfdBatchGetContact for those.  A batch with a table of per-instance parameters uses the instance's
+ * own masses, centres of mass and inertias.
+ * RKFD_DYN_ROTOR (with RKFD_DYN_MASS) adds mot_gear^2 x mot_inertia of the DC-motor joints to the diagonal, the reflected rotor and
+ * gear inertia of DEVIATIONS.md item 5: with it M acc + h closes against the step's own accelerations with the motor's torque less
+ * that term; without it M is the rigid-body matrix.
+ * Worlds of more than 64 joint coordinates are refused at the first call with a message, as the Jacobians refuse them; so is a world
+ * whose tables for one instance exceed the LDS of a workgroup (the message names the bytes).
+ * A batch that never calls these allocates nothing and launches nothing; snapshot / restore / reset do not touch the results
+ * (derived data). */
+enum { RKFD_DYN_MASS = 1, RKFD_DYN_BIAS = 2, RKFD_DYN_GRAVITY = 4, RKFD_DYN_ROTOR = 8 };
+/* computes the selected quantities from the live state, in stream order after everything the batch has launched (joins the internal
+ * split streams onto `stream` first, as rkfdBatchUpdateLinks does); asynchronous; changes no state.  -1 with a message for flags 0,
+ * unknown bits, or RKFD_DYN_ROTOR without RKFD_DYN_MASS */
+int rkfdBatchUpdateDynamics(rkfdBatch *b, int flags, void *stream);
+/* host copies of the last rkfdBatchUpdateDynamics (waits for it); any pointer may be NULL; -1 with a message when a requested
+ * quantity was not part of the last launch or none was made */
+int rkfdBatchGetDynamics(rkfdBatch *b, double *M, double *h, double *g);
+/* device pointers to the same buffers (owned by the batch, allocated at the first launch that needs them, stable afterwards; NULL
+ * before) */
+const double *rkfdBatchDevMassMatrix(rkfdBatch *b);
+const double *rkfdBatchDevBias(rkfdBatch *b);
+const double *rkfdBatchDevGravity(rkfdBatch *b);
+
 /* ---- the node level: all the GPUs of one node from ONE process, host code in C -------------------------------------
  * SURVEY 8e / north star: "independent MPC-style rollouts shard embarrassingly across the 8 GPUs of one node with an
  * RCCL-over-xGMI gather of final states only".  The instances of a batch are independent (one rkFD never references another),
@@ -384,6 +425,9 @@ int rkfdNodeGetLinks(rkfdNode *n, int flags, double *R, double *p, double *v, do
  * in instance order (shapes as rkfdBatchGetJacobians with batch = total; the pointer of a quantity `flags` does not select must be NULL) */
 int rkfdNodeSetJacobianSites(rkfdNode *n, int nsite, const int *link, const double *point);
 int rkfdNodeGetJacobians(rkfdNode *n, int flags, double *J, double *Jcom);
+/* rkfdBatchUpdateDynamics( flags ) on every device's own thread and stream, then host arrays over ALL instances in instance order
+ * (shapes as rkfdBatchGetDynamics with batch = total; pointers of quantities `flags` does not select must be NULL) */
+int rkfdNodeGetDynamics(rkfdNode *n, int flags, double *M, double *h, double *g);
 /* one ncclAllGather of the final {dis, vel}: afterwards every device holds all `total` final states (rkfdNodeGatherDev: on
  * device k, [ndev][mx][2 ndof] doubles - block j = shard j's instances, dis | vel per instance, padded to the largest shard mx),
  * and dis / vel ([total][ndof], either may be NULL) receive them on the host in instance order */

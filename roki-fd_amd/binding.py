@@ -134,6 +134,11 @@ def lib():
     for f in ("rkfdBatchDevJacobian", "rkfdBatchDevComJacobian"):
         getattr(L, f).argtypes = [vp]
         getattr(L, f).restype = vp
+    L.rkfdBatchUpdateDynamics.argtypes = [vp, C.c_int, vp]; L.rkfdBatchGetDynamics.argtypes = [vp, vp, vp, vp]
+    L.rkfdNodeGetDynamics.argtypes = [vp, C.c_int, vp, vp, vp]
+    for f in ("rkfdBatchDevMassMatrix", "rkfdBatchDevBias", "rkfdBatchDevGravity"):
+        getattr(L, f).argtypes = [vp]
+        getattr(L, f).restype = vp
     L.rkfdNodeCreate.argtypes = [C.POINTER(RkfdModel), C.c_int, C.c_int, C.c_int, vp]; L.rkfdNodeCreate.restype = vp
     L.rkfdNodeDestroy.argtypes = [vp]
     for f in ("rkfdNodeDevices", "rkfdNodeSize", "rkfdNodeSpecialize", "rkfdNodeUpdateInit", "rkfdNodeSnapshot", "rkfdNodeRestore", "rkfdNodeStatus"):
@@ -258,6 +263,18 @@ def _jac_arrays(n, ns, nc, nd, flags):
     return {k: np.empty(shapes[k]) for k, f in _JAC_KEYS if flags & f}
 
 
+# joint-space dynamics (include/rkfd_hip.h: RKFD_DYN_*): what update_dynamics computes and get_dynamics returns
+DYN_MASS, DYN_BIAS, DYN_GRAVITY, DYN_ROTOR = 1, 2, 4, 8
+DYN_ALL = DYN_MASS | DYN_BIAS | DYN_GRAVITY
+_DYN_KEYS = (("M", DYN_MASS), ("h", DYN_BIAS), ("g", DYN_GRAVITY))
+
+
+def _dyn_arrays(n, nd, flags):
+    """host arrays of the dynamics over n instances: {name: array} of the quantities `flags` selects"""
+    shapes = {"M": (n, nd, nd), "h": (n, nd), "g": (n, nd)}
+    return {k: np.empty(shapes[k]) for k, f in _DYN_KEYS if flags & f}
+
+
 # per-instance reset (include/rkfd_hip.h: RKFD_RESET_*): slot values besides the rows 0 .. nslots-1 of the bank
 RESET_KEEP, RESET_SNAPSHOT = -1, -2
 
@@ -318,6 +335,7 @@ class Batch:
         self.nchain = m.nchain
         self._links_flags = 0          # what the last update_links() computed
         self._jac_flags = 0            # what the last update_jacobians() computed, of the present sites
+        self._dyn_flags = 0            # what the last update_dynamics() computed
         self.device = device
         self._ctrl_keep = []           # device schedules of update_controlled() the launches issued since the last join / sync read
         self._owned = _handle is None
@@ -624,6 +642,38 @@ class Batch:
         shapes = ((self.B, self.nsite, 6, self.ndof), (self.B, self.nchain, 3, self.ndof))
         return {k: torch.as_tensor(_View(p, sh), device="cuda") if p else None for (k, _), p, sh in zip(_JAC_KEYS, self.jacobian_ptrs(), shapes)}
 
+    def update_dynamics(self, flags=DYN_ALL, stream=None):
+        """joint-space dynamics ON THE DEVICE from the live state: the inertia matrix M (DYN_MASS) with respect to the packed joint
+        RATES, the bias force h = rnea(q, qd, 0) (DYN_BIAS) and the gravity force g (DYN_GRAVITY), M qdd + h = generalised force;
+        DYN_ROTOR adds the reflected rotor inertia of the DC-motor joints to M's diagonal.  One kernel launch in stream order after
+        everything the batch has launched (no host wait, no state changed); get_dynamics() / dynamics_tensors() hand the results out."""
+        self._chk(self._L.rkfdBatchUpdateDynamics(self._b, int(flags), stream))
+        self._dyn_flags = int(flags)
+
+    def get_dynamics(self):
+        """host copies of the last update_dynamics(): a dict with (of what its flags selected) M [B, ndof, ndof], h and g [B, ndof],
+        rows and columns in the order of the packed rate vector"""
+        if not self._dyn_flags:
+            raise RkfdError("get_dynamics: no dynamics have been computed (update_dynamics)")
+        out = _dyn_arrays(self.B, self.ndof, self._dyn_flags)
+        self._chk(self._L.rkfdBatchGetDynamics(self._b, *[_ptr(out.get(k)) for k, _ in _DYN_KEYS]))
+        return out
+
+    def dynamics_ptrs(self):
+        """device addresses of M, h and g (None for a buffer no update_dynamics() has needed yet; stable once allocated)"""
+        return tuple(getattr(self._L, f)(self._b) for f in ("rkfdBatchDevMassMatrix", "rkfdBatchDevBias", "rkfdBatchDevGravity"))
+
+    def dynamics_tensors(self):
+        """the dynamics' buffers as a dict of zero-copy float64 torch views, M [B, ndof, ndof], h and g [B, ndof] (None where no
+        update_dynamics() has needed the buffer yet)"""
+        import torch
+
+        class _View:
+            def __init__(self, ptr, shape):
+                self.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(int(ptr), False), version=2, strides=None)
+        shapes = ((self.B, self.ndof, self.ndof), (self.B, self.ndof), (self.B, self.ndof))
+        return {k: torch.as_tensor(_View(p, sh), device="cuda") if p else None for (k, _), p, sh in zip(_DYN_KEYS, self.dynamics_ptrs(), shapes)}
+
     def dev_tensors(self, links=False):
         """torch tensors ALIASING the live device state [B, ndof] (dis, vel, acc): zero-copy views
         for consumers on the device, e.g. the RCCL all-gather of final states.  links=True: the buffers of the task-space
@@ -794,6 +844,13 @@ class Node:
         ns = max(self._L.rkfdBatchJacobianSiteNum(self._L.rkfdNodeBatch(self._n, 0)), 0)
         out = _jac_arrays(self.total, ns, self.nchain, self.ndof, int(flags))
         self._chk(self._L.rkfdNodeGetJacobians(self._n, int(flags), *[_ptr(out.get(k)) for k, _ in _JAC_KEYS]))
+        return out
+
+    def get_dynamics(self, flags=DYN_ALL):
+        """Batch.update_dynamics(flags) on every device's own thread and stream, then the results of ALL instances in instance
+        order, as Batch.get_dynamics() returns them"""
+        out = _dyn_arrays(self.total, self.ndof, int(flags))
+        self._chk(self._L.rkfdNodeGetDynamics(self._n, int(flags), *[_ptr(out.get(k)) for k, _ in _DYN_KEYS]))
         return out
 
     def gather(self):

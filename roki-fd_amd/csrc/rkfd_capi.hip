@@ -19,6 +19,7 @@
 #include "rkfd_devmodel_host.h"
 #include "readout/rkfd_links_host.h"   /* the task-space read-out (rkfd_capi_links.hip) */
 #include "readout/rkfd_jac_host.h"     /* the task-space Jacobians (rkfd_capi_jac.hip) */
+#include "readout/rkfd_dyn_host.h"     /* the joint-space dynamics (rkfd_capi_dyn.hip) */
 #include "reset/rkfd_reset_host.h"     /* the per-instance reset and its bank of start states (rkfd_capi_reset.hip) */
 #include "rkfd_device_src.inc"       /* the device headers as string literals (tools/embed_sources.py), for hipRTC */
 
@@ -165,6 +166,9 @@ struct rkfdBatch {
   /* rkfdBatchSetJacobianSites / UpdateJacobians: the Jacobians' tables, sites and result buffers (rkfd_capi_jac.hip), made by the
    * first of those calls - a batch that never asks has none */
   rkfdJac *jac;
+  /* rkfdBatchUpdateDynamics: the joint-space dynamics' tables and result buffers (rkfd_capi_dyn.hip), made by the first launch - a
+   * batch that never asks has none */
+  rkfdDyn *dyn;
   /* rkfdBatchBankReserve / rkfdBatchReset: the bank of start states and the staging of the slot values (rkfd_capi_reset.hip), made by
    * the first of those calls - a batch that never resets one instance alone has none */
   rkfdReset *reset;
@@ -277,6 +281,7 @@ extern "C" void rkfdBatchDestroy(rkfdBatch *b)
   (void)hipFree( b->d_par ); for( int k=0; k<RKFD_PAR_COUNT; k++ ) free( b->h_par[k] );
   rkfd_links_destroy( b->links );
   rkfd_jac_destroy( b->jac );
+  rkfd_dyn_destroy( b->dyn );
   rkfd_reset_destroy( b->reset );
   if( b->spec_mod ) (void)hipModuleUnload( b->spec_mod );
   (void)hipFree( b->d_err ); (void)hipFree( b->dblob ); (void)hipFree( b->dblob2 );
@@ -1498,5 +1503,45 @@ extern "C" int rkfdBatchGetJacobians(rkfdBatch *b, double *J, double *Jcom)
 }
 extern "C" const double *rkfdBatchDevJacobian(rkfdBatch *b){ return b ? rkfd_jac_dev( b->jac, 0 ) : NULL; }
 extern "C" const double *rkfdBatchDevComJacobian(rkfdBatch *b){ return b ? rkfd_jac_dev( b->jac, 1 ) : NULL; }
+
+/* ---- joint-space dynamics: mass matrix, bias and gravity forces on the device ---------------------------------- */
+/* One launch of rkfd_dyn_kernel in stream order after everything the batch has launched: the internal split streams are joined
+ * onto `stream` first (as rkfdBatchJoin does), no host wait.  It reads dis / vel and writes the dynamics' own buffers only. */
+extern "C" int rkfdBatchUpdateDynamics(rkfdBatch *b, int flags, void *stream)
+{
+  if( !b ){ SETERR( "rkfdBatchUpdateDynamics: null batch" ); return -1; }
+  if( flags <= 0 || ( flags & ~( RKFD_DYN_MASS | RKFD_DYN_BIAS | RKFD_DYN_GRAVITY | RKFD_DYN_ROTOR ) ) ){ SETERR( "rkfdBatchUpdateDynamics: flags must be a combination of RKFD_DYN_MASS, RKFD_DYN_BIAS, RKFD_DYN_GRAVITY and RKFD_DYN_ROTOR (got %d)", flags ); return -1; }
+  if( ( flags & RKFD_DYN_ROTOR ) && !( flags & RKFD_DYN_MASS ) ){ SETERR( "rkfdBatchUpdateDynamics: RKFD_DYN_ROTOR without RKFD_DYN_MASS (the rotor inertia is added to the diagonal of M)" ); return -1; }
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  char err[400] = "";
+  if( !b->dyn ){
+    b->dyn = rkfd_dyn_create( b->model_for_w2, b->batch, err, sizeof(err) );
+    if( !b->dyn ){ SETERR( "%s", err ); return -1; }
+  }
+  if( join_streams( b, (hipStream_t)stream ) < 0 ) return -1;
+  b->last_stream = (hipStream_t)stream; b->launched = 1;
+  if( rkfd_dyn_launch( b->dyn, b->st.dis, b->st.vel, flags, b->d_par ? b->h_par[RKFD_PAR_MASS] : NULL, b->d_par ? b->h_par[RKFD_PAR_COM] : NULL,
+                       b->d_par ? b->h_par[RKFD_PAR_INERTIA] : NULL, b->par_gen, stream, err, sizeof(err) ) < 0 ){ SETERR( "rkfdBatchUpdateDynamics: %s", err ); return -1; }
+  return 0;
+}
+extern "C" int rkfdBatchGetDynamics(rkfdBatch *b, double *M, double *h, double *g)
+{
+  if( !b ){ SETERR( "rkfdBatchGetDynamics: null batch" ); return -1; }
+  const int have = rkfd_dyn_flags( b->dyn );
+  if( !have ){ SETERR( "rkfdBatchGetDynamics: no dynamics have been computed (rkfdBatchUpdateDynamics)" ); return -1; }
+  if( ( M && !( have & RKFD_DYN_MASS ) ) || ( h && !( have & RKFD_DYN_BIAS ) ) || ( g && !( have & RKFD_DYN_GRAVITY ) ) ){
+    SETERR( "rkfdBatchGetDynamics: the last rkfdBatchUpdateDynamics (flags %d) did not compute %s", have,
+            ( M && !( have & RKFD_DYN_MASS ) ) ? "the mass matrix (RKFD_DYN_MASS)" : ( h && !( have & RKFD_DYN_BIAS ) ) ? "the bias force (RKFD_DYN_BIAS)" : "the gravity force (RKFD_DYN_GRAVITY)" );
+    return -1;
+  }
+  if( !M && !h && !g ) return 0;
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  char err[400] = "";
+  if( rkfd_dyn_get( b->dyn, M, h, g, err, sizeof(err) ) < 0 ){ SETERR( "rkfdBatchGetDynamics: %s", err ); return -1; }
+  return 0;
+}
+extern "C" const double *rkfdBatchDevMassMatrix(rkfdBatch *b){ return b ? rkfd_dyn_dev( b->dyn, 0 ) : NULL; }
+extern "C" const double *rkfdBatchDevBias(rkfdBatch *b){ return b ? rkfd_dyn_dev( b->dyn, 1 ) : NULL; }
+extern "C" const double *rkfdBatchDevGravity(rkfdBatch *b){ return b ? rkfd_dyn_dev( b->dyn, 2 ) : NULL; }
 
 #include "rkfd_capi_node.inc"      /* the node level: one host thread + stream per device, one RCCL all-gather of final states */
