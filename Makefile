@@ -34,7 +34,7 @@ DEVSRC = include/rkfd_model.h $(CSRC)/rkfd_devmodel.h $(CSRC)/rkfd_device.h $(so
 $(BUILD)/rkfd_device_src.inc: $(DEVSRC) tools/embed_sources.py | $(BUILD)
 	python3 tools/embed_sources.py $@ $(DEVSRC)
 
-$(BUILD)/rkfd_capi.o: $(CSRC)/rkfd_capi.hip $(CSRC)/rkfd_capi_node.inc $(BUILD)/rkfd_device_src.inc $(CSRC)/*.h $(CSRC)/device/*.h $(CSRC)/readout/rkfd_links_host.h $(CSRC)/readout/rkfd_jac_host.h $(CSRC)/readout/rkfd_dyn_host.h $(CSRC)/reset/rkfd_reset_host.h include/*.h | $(BUILD)
+$(BUILD)/rkfd_capi.o: $(CSRC)/rkfd_capi.hip $(CSRC)/rkfd_capi_node.inc $(BUILD)/rkfd_device_src.inc $(CSRC)/*.h $(CSRC)/device/*.h $(CSRC)/readout/rkfd_links_host.h $(CSRC)/readout/rkfd_jac_host.h $(CSRC)/readout/rkfd_dyn_host.h $(CSRC)/readout/rkfd_cf_host.h $(CSRC)/reset/rkfd_reset_host.h include/*.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(BUILD)/rkfd_capi.remarks || ( cat $(BUILD)/rkfd_capi.remarks; exit 1 )
 	@grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|VGPRs Spill|SGPRs Spill" $(BUILD)/rkfd_capi.remarks | sed 's/.*remark: *//; s/ \[-Rpass.*//' > $(PKG)/kernel_resources.txt
 	@grep -vE "remark:|^ +[0-9]+ \||^ +\||\^" $(BUILD)/rkfd_capi.remarks || true
@@ -59,12 +59,17 @@ $(BUILD)/rkfd_capi_dyn.o: $(CSRC)/rkfd_capi_dyn.hip $(CSRC)/readout/rkfd_dyn.h $
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(BUILD)/rkfd_capi_dyn.remarks || ( cat $(BUILD)/rkfd_capi_dyn.remarks; exit 1 )
 	@grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|VGPRs Spill|SGPRs Spill" $(BUILD)/rkfd_capi_dyn.remarks | sed 's/.*remark: *//; s/ \[-Rpass.*//' > $(PKG)/kernel_resources_dyn.txt
 
+# the contact read-out (rkfdBatchUpdateContactForces): a kernel and a translation unit of its own, like the dynamics: its own report
+$(BUILD)/rkfd_capi_cf.o: $(CSRC)/rkfd_capi_cf.hip $(CSRC)/readout/rkfd_cf.h $(CSRC)/readout/rkfd_cf_host.h $(CSRC)/readout/rkfd_jac.h $(CSRC)/*.h $(CSRC)/device/rkfd_dev_base.h include/*.h | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(BUILD)/rkfd_capi_cf.remarks || ( cat $(BUILD)/rkfd_capi_cf.remarks; exit 1 )
+	@grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|VGPRs Spill|SGPRs Spill" $(BUILD)/rkfd_capi_cf.remarks | sed 's/.*remark: *//; s/ \[-Rpass.*//' > $(PKG)/kernel_resources_cf.txt
+
 # the per-instance reset (rkfdBatchReset) and its bank of start states: a kernel and a translation unit of its own, like the read-out: its own report
 $(BUILD)/rkfd_capi_reset.o: $(CSRC)/rkfd_capi_reset.hip $(CSRC)/reset/*.h $(CSRC)/rkfd_devmodel.h include/*.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(BUILD)/rkfd_capi_reset.remarks || ( cat $(BUILD)/rkfd_capi_reset.remarks; exit 1 )
 	@grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|VGPRs Spill|SGPRs Spill" $(BUILD)/rkfd_capi_reset.remarks | sed 's/.*remark: *//; s/ \[-Rpass.*//' > $(PKG)/kernel_resources_reset.txt
 
-$(LIB): $(HOST_OBJS) $(BUILD)/rkfd_capi.o $(BUILD)/rkfd_capi_par.o $(BUILD)/rkfd_capi_links.o $(BUILD)/rkfd_capi_reset.o $(BUILD)/rkfd_capi_jac.o $(BUILD)/rkfd_capi_dyn.o
+$(LIB): $(HOST_OBJS) $(BUILD)/rkfd_capi.o $(BUILD)/rkfd_capi_par.o $(BUILD)/rkfd_capi_links.o $(BUILD)/rkfd_capi_reset.o $(BUILD)/rkfd_capi_jac.o $(BUILD)/rkfd_capi_dyn.o $(BUILD)/rkfd_capi_cf.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl -lpthread
 
 oracle:
@@ -77,7 +82,7 @@ spec: $(LIB)
 
 emu: tests/emu/librkfd_emu.so tests/emu/librkfd_emu_w2.so tests/emu/librkfd_emu_ctrl.so tests/emu/librkfd_emu_ctrl_w2.so \
      tests/emu/librkfd_emu_par.so tests/emu/librkfd_emu_par_w2.so tests/emu/librkfd_emu_links.so tests/emu/librkfd_emu_reset.so \
-     tests/emu/librkfd_emu_jac.so tests/emu/librkfd_emu_dyn.so
+     tests/emu/librkfd_emu_jac.so tests/emu/librkfd_emu_dyn.so tests/emu/librkfd_emu_cf.so
 
 tests/emu/librkfd_emu.so: tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_device.h $(CSRC)/rkfd_devmodel.cpp $(CSRC)/*.h $(CSRC)/device/*.h include/*.h
 	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread $(INC) -o $@ tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_devmodel.cpp
@@ -112,12 +117,16 @@ tests/emu/librkfd_emu_jac.so: tests/emu/rkfd_emu_jac.cpp tests/emu/rkfd_emu.cpp 
 tests/emu/librkfd_emu_dyn.so: tests/emu/rkfd_emu_dyn.cpp tests/emu/rkfd_emu.cpp $(CSRC)/readout/*.h $(CSRC)/rkfd_device.h $(CSRC)/rkfd_devmodel.cpp $(CSRC)/*.h $(CSRC)/device/*.h include/*.h
 	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread $(INC) -o $@ tests/emu/rkfd_emu_dyn.cpp $(CSRC)/rkfd_devmodel.cpp
 
+# the harness of the contact read-out (readout/rkfd_cf.h, the device code of rkfdBatchUpdateContactForces)
+tests/emu/librkfd_emu_cf.so: tests/emu/rkfd_emu_cf.cpp tests/emu/rkfd_emu.cpp $(CSRC)/readout/*.h $(CSRC)/rkfd_device.h $(CSRC)/rkfd_devmodel.cpp $(CSRC)/*.h $(CSRC)/device/*.h include/*.h
+	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread $(INC) -o $@ tests/emu/rkfd_emu_cf.cpp $(CSRC)/rkfd_devmodel.cpp
+
 # the harness of the per-instance reset (reset/rkfd_reset.h, the device code of rkfdBatchReset)
 tests/emu/librkfd_emu_reset.so: tests/emu/rkfd_emu_reset.cpp $(CSRC)/reset/rkfd_reset.h $(CSRC)/rkfd_devmodel.h include/*.h
 	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread $(INC) -o $@ tests/emu/rkfd_emu_reset.cpp
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(PKG)/spec $(PKG)/kernel_resources_links.txt tests/emu/librkfd_emu_links.so $(PKG)/kernel_resources_reset.txt tests/emu/librkfd_emu_reset.so $(PKG)/kernel_resources_jac.txt tests/emu/librkfd_emu_jac.so $(PKG)/kernel_resources_dyn.txt tests/emu/librkfd_emu_dyn.so tests/emu/librkfd_emu.so tests/emu/librkfd_emu_w2.so tests/emu/librkfd_emu_ctrl.so tests/emu/librkfd_emu_ctrl_w2.so tests/emu/librkfd_emu_par.so tests/emu/librkfd_emu_par_w2.so
+	rm -rf $(BUILD) $(LIB) $(PKG)/spec $(PKG)/kernel_resources_links.txt tests/emu/librkfd_emu_links.so $(PKG)/kernel_resources_reset.txt tests/emu/librkfd_emu_reset.so $(PKG)/kernel_resources_jac.txt tests/emu/librkfd_emu_jac.so $(PKG)/kernel_resources_dyn.txt tests/emu/librkfd_emu_dyn.so $(PKG)/kernel_resources_cf.txt tests/emu/librkfd_emu_cf.so tests/emu/librkfd_emu.so tests/emu/librkfd_emu_w2.so tests/emu/librkfd_emu_ctrl.so tests/emu/librkfd_emu_ctrl_w2.so tests/emu/librkfd_emu_par.so tests/emu/librkfd_emu_par_w2.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle emu spec clean

@@ -50,7 +50,8 @@ int rkfdBatchDof(const rkfdBatch *b);
  * launches made before the call left.  Launches a caller spread over FURTHER streams of its own must be joined by the caller first
  * (rkfdBatchStatus on each, or its own events): only the stream of the last launch is known to the batch.  That stream must
  * still exist at the first accessor (or rkfdBatchStatus on it) after the launch: destroy it only after one of them has returned.
- * An error the launch left on the stream is the accessor's error. */
+ * An error the launch left on the stream is the accessor's error.  rkfdBatchUpdateContactForces and rkfdBatchUpdateContactForcesDev
+ * are launches in this sense too: the accessors wait for the stream they were given as for any of the above. */
 /* rkFDChainSetDis / rkFDChainSetVel (reference src/rkfd_sim.c:277-287), all instances at once:
  * dis, vel are [batch][ndof] */
 int rkfdBatchSetState(rkfdBatch *b, const double *dis, const double *vel);
@@ -367,6 +368,45 @@ const double *rkfdBatchDevMassMatrix(rkfdBatch *b);
 const double *rkfdBatchDevBias(rkfdBatch *b);
 const double *rkfdBatchDevGravity(rkfdBatch *b);
 
+/* ---- contact read-out: the contact term J_c' f of the equation of motion, computed ON THE DEVICE --------------------------------
+ * The step kernels keep the force of every candidate contact vertex (rkfdBatchGetContact: a synchronous host copy, indexed by
+ * candidate).  One kernel launch (rkfd_cf_kernel, a kernel of its own: the step kernels, the read-out, the Jacobians and the dynamics
+ * are untouched) turns them, for every instance from its live dis, into what an observation, a termination test or a whole-body
+ * controller needs, in MODEL space - model links as rkfdModel numbers them, the packed joint rates of the columns of J and M:
+ *   point  [batch][ncand][3]   the world position x_j = p_own + R_own v_j of every candidate vertex, active or not
+ *   wrench [batch][nlink][6]   the net contact wrench on every model link in world axes: rows 0-2 the force, rows 3-5 the moment about
+ *                              the link's own origin (the p of rkfdBatchUpdateLinks).  An active candidate j gives +f_j at x_j to the
+ *                              link that owns the vertex (cand_side) and -f_j at x_j to the other link of its pair; links of chains
+ *                              without coordinates (a floor) get theirs too
+ *   count  [batch][nlink]      (int) the active candidates that touch the link, on either side
+ *   genf   [batch][ndof]       sum_j J_j' f_j = sum_l J_l[0:3]' F_l + J_l[3:6]' N_l with J_l what rkfdBatchUpdateJacobians gives for the
+ *                              site ( link l, its origin ) and ( F_l, N_l ) the row of wrench: M qdd + h = tau + genf.  Exactly 0.0 on
+ *                              coordinates whose link is no ancestor of a touched link; a breakable float joint gets its six entries
+ *                              whether it has broken or not, as in J
+ * A candidate whose flag is 0 contributes nothing, whatever its force entry holds (the step leaves stale values there).  No mass and
+ * no other per-instance parameter enters.  Worlds under the Volume plugin are refused at the first call with a message (that plugin
+ * produces no per-vertex forces), as are worlds of more than 64 joint coordinates and worlds whose tables for one instance exceed the
+ * LDS of a workgroup (the message names the bytes).  A batch that never calls these allocates nothing and launches nothing; snapshot /
+ * restore / reset do not touch the results (derived data). */
+enum { RKFD_CF_POINT = 1, RKFD_CF_WRENCH = 2, RKFD_CF_GENF = 4 };
+/* computes the selected quantities (RKFD_CF_WRENCH: wrench and count) from the live dis and the batch's own candidate flags and forces,
+ * in stream order after everything the batch has launched (joins the internal split streams onto `stream` first, as
+ * rkfdBatchUpdateLinks does); asynchronous; changes no state.  -1 with a message for flags 0 or unknown bits */
+int rkfdBatchUpdateContactForces(rkfdBatch *b, int flags, void *stream);
+/* the same launch with the flags and forces of the caller - hypothesised forces of a contact-implicit controller, or of a solver of
+ * its own -: active_dev [batch][ncand] (int), f_dev [batch][ncand*3] on the batch's device, read in stream order after `stream` (no
+ * copy); they must stay unchanged until the launch is done (rkfdBatchStatus on that stream, or any accessor) */
+int rkfdBatchUpdateContactForcesDev(rkfdBatch *b, int flags, const int *active_dev, const double *f_dev, void *stream);
+/* host copies of the last launch (waits for it); any pointer may be NULL; -1 with a message when a requested quantity was not part of
+ * the last launch or none was made */
+int rkfdBatchGetContactForces(rkfdBatch *b, double *point, double *wrench, int *count, double *genf);
+/* device pointers to the same buffers (owned by the batch, allocated at the first launch that needs them, stable afterwards; NULL
+ * before) */
+const double *rkfdBatchDevContactPoint(rkfdBatch *b);
+const double *rkfdBatchDevContactWrench(rkfdBatch *b);
+const int *rkfdBatchDevContactCount(rkfdBatch *b);
+const double *rkfdBatchDevContactGenForce(rkfdBatch *b);
+
 /* ---- the node level: all the GPUs of one node from ONE process, host code in C -------------------------------------
  * SURVEY 8e / north star: "independent MPC-style rollouts shard embarrassingly across the 8 GPUs of one node with an
  * RCCL-over-xGMI gather of final states only".  The instances of a batch are independent (one rkFD never references another),
@@ -428,6 +468,9 @@ int rkfdNodeGetJacobians(rkfdNode *n, int flags, double *J, double *Jcom);
 /* rkfdBatchUpdateDynamics( flags ) on every device's own thread and stream, then host arrays over ALL instances in instance order
  * (shapes as rkfdBatchGetDynamics with batch = total; pointers of quantities `flags` does not select must be NULL) */
 int rkfdNodeGetDynamics(rkfdNode *n, int flags, double *M, double *h, double *g);
+/* rkfdBatchUpdateContactForces( flags ) on every device's own thread and stream, then host arrays over ALL instances in instance
+ * order (shapes as rkfdBatchGetContactForces with batch = total; pointers of quantities `flags` does not select must be NULL) */
+int rkfdNodeGetContactForces(rkfdNode *n, int flags, double *point, double *wrench, int *count, double *genf);
 /* one ncclAllGather of the final {dis, vel}: afterwards every device holds all `total` final states (rkfdNodeGatherDev: on
  * device k, [ndev][mx][2 ndof] doubles - block j = shard j's instances, dis | vel per instance, padded to the largest shard mx),
  * and dis / vel ([total][ndof], either may be NULL) receive them on the host in instance order */

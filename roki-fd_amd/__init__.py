@@ -9,7 +9,7 @@ from .binding import (  # noqa: F401
     LIB_PATH, lib, RkfdModel, World, Batch, Node, RkfdError, PARAM_NAMES, param_key,
     JOINT_FIXED, JOINT_REVOL, JOINT_PRISM, JOINT_FLOAT, JOINT_SPHER, JOINT_BRFLOAT,
     LINKS_POSE, LINKS_VEL, LINKS_COM, LINKS_ALL, JAC_SITES, JAC_COM, JAC_ALL,
-    DYN_MASS, DYN_BIAS, DYN_GRAVITY, DYN_ROTOR, DYN_ALL, RESET_KEEP, RESET_SNAPSHOT, reset_slots,
+    DYN_MASS, DYN_BIAS, DYN_GRAVITY, DYN_ROTOR, DYN_ALL, CF_POINT, CF_WRENCH, CF_GENF, CF_ALL, RESET_KEEP, RESET_SNAPSHOT, reset_slots,
     SOLVER_VERT, SOLVER_MLCP, SOLVER_VOLUME, CONTACT_RIGID, CONTACT_ELASTIC, SF, KF,
 )
 from . import binding  # noqa: F401

@@ -139,6 +139,11 @@ def lib():
     for f in ("rkfdBatchDevMassMatrix", "rkfdBatchDevBias", "rkfdBatchDevGravity"):
         getattr(L, f).argtypes = [vp]
         getattr(L, f).restype = vp
+    L.rkfdBatchUpdateContactForces.argtypes = [vp, C.c_int, vp]; L.rkfdBatchUpdateContactForcesDev.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.rkfdBatchGetContactForces.argtypes = [vp, vp, vp, vp, vp]; L.rkfdNodeGetContactForces.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    for f in _CF_DEV:
+        getattr(L, f).argtypes = [vp]
+        getattr(L, f).restype = vp
     L.rkfdNodeCreate.argtypes = [C.POINTER(RkfdModel), C.c_int, C.c_int, C.c_int, vp]; L.rkfdNodeCreate.restype = vp
     L.rkfdNodeDestroy.argtypes = [vp]
     for f in ("rkfdNodeDevices", "rkfdNodeSize", "rkfdNodeSpecialize", "rkfdNodeUpdateInit", "rkfdNodeSnapshot", "rkfdNodeRestore", "rkfdNodeStatus"):
@@ -275,6 +280,52 @@ def _dyn_arrays(n, nd, flags):
     return {k: np.empty(shapes[k]) for k, f in _DYN_KEYS if flags & f}
 
 
+# contact read-out (include/rkfd_hip.h: RKFD_CF_*): what update_contact_forces computes and get_contact_forces returns
+CF_POINT, CF_WRENCH, CF_GENF = 1, 2, 4
+CF_ALL = CF_POINT | CF_WRENCH | CF_GENF
+_CF_KEYS = (("point", CF_POINT), ("wrench", CF_WRENCH), ("count", CF_WRENCH), ("genf", CF_GENF))
+_CF_DEV = ("rkfdBatchDevContactPoint", "rkfdBatchDevContactWrench", "rkfdBatchDevContactCount", "rkfdBatchDevContactGenForce")
+
+
+def _cf_shapes(n, nc, nl, nd):
+    return {"point": (n, nc, 3), "wrench": (n, nl, 6), "count": (n, nl), "genf": (n, nd)}
+
+
+def _cf_arrays(n, nc, nl, nd, flags):
+    """host arrays of the contact read-out over n instances: {name: array} of the quantities `flags` selects (count: int32)"""
+    shapes = _cf_shapes(n, nc, nl, nd)
+    return {k: np.empty(shapes[k], dtype=np.int32 if k == "count" else np.float64) for k, f in _CF_KEYS if flags & f}
+
+
+def _cf_dev_ptr(name, t, typestr, shapes, device):
+    """device address of an argument of update_contact_forces, checked before any library call: a contiguous torch tensor on
+    cuda:`device`, or any object with a __cuda_array_interface__ (contiguous; its device is the caller's word)"""
+    if type(t).__module__.split(".")[0] == "torch":
+        import torch
+        want = {"<i4": torch.int32, "<f8": torch.float64}[typestr]
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"update_contact_forces: {name} of type {type(t).__name__}: expected a torch tensor")
+        if tuple(t.shape) not in shapes:
+            raise ValueError(f"update_contact_forces: {name} of shape {tuple(t.shape)}: expected {shapes[0]}")
+        if t.dtype != want:
+            raise TypeError(f"update_contact_forces: {name} of dtype {t.dtype}: expected {want}")
+        if t.device.type != "cuda" or t.device.index != device:
+            raise ValueError(f"update_contact_forces: {name} on {t.device}: expected cuda:{device}")
+        if not t.is_contiguous():
+            raise ValueError(f"update_contact_forces: {name} must be contiguous")
+        return t.data_ptr()
+    cai = getattr(t, "__cuda_array_interface__", None)
+    if cai is None:
+        raise TypeError(f"update_contact_forces: {name} of type {type(t).__name__}: expected a torch tensor on the device (or an object with a __cuda_array_interface__)")
+    if tuple(cai["shape"]) not in shapes:
+        raise ValueError(f"update_contact_forces: {name} of shape {tuple(cai['shape'])}: expected {shapes[0]}")
+    if cai["typestr"] != typestr:
+        raise TypeError(f"update_contact_forces: {name} of type {cai['typestr']}: expected {typestr}")
+    if cai.get("strides") is not None:
+        raise ValueError(f"update_contact_forces: {name} must be contiguous")
+    return int(cai["data"][0])
+
+
 # per-instance reset (include/rkfd_hip.h: RKFD_RESET_*): slot values besides the rows 0 .. nslots-1 of the bank
 RESET_KEEP, RESET_SNAPSHOT = -1, -2
 
@@ -336,6 +387,7 @@ class Batch:
         self._links_flags = 0          # what the last update_links() computed
         self._jac_flags = 0            # what the last update_jacobians() computed, of the present sites
         self._dyn_flags = 0            # what the last update_dynamics() computed
+        self._cf_flags = 0             # what the last update_contact_forces() computed
         self.device = device
         self._ctrl_keep = []           # device schedules of update_controlled() the launches issued since the last join / sync read
         self._owned = _handle is None
@@ -674,6 +726,56 @@ class Batch:
         shapes = ((self.B, self.ndof, self.ndof), (self.B, self.ndof), (self.B, self.ndof))
         return {k: torch.as_tensor(_View(p, sh), device="cuda") if p else None for (k, _), p, sh in zip(_DYN_KEYS, self.dynamics_ptrs(), shapes)}
 
+    def update_contact_forces(self, flags=CF_ALL, stream=None, active=None, f=None):
+        """contact read-out ON THE DEVICE from the live joint coordinates and the force of every candidate contact vertex: the world
+        position of every candidate vertex (CF_POINT), the net contact wrench and the number of active candidates of every model
+        link (CF_WRENCH) and the generalised contact force J_c' f on the packed joint rates (CF_GENF).  One kernel launch in stream
+        order after everything the batch has launched (no host wait, no state changed).  active / f: the caller's own flags and
+        forces in place of the batch's, contiguous int32 (B, ncand) and float64 (B, ncand, 3) torch tensors on the batch's device
+        (or other objects with a __cuda_array_interface__ of those shapes and types), read in place in order after `stream`
+        (default for tensors: torch.cuda.current_stream()); the batch keeps a reference to them until join() or a synchronous
+        accessor.  get_contact_forces() / contact_force_tensors() hand the results out."""
+        if active is None and f is None:
+            self._chk(self._L.rkfdBatchUpdateContactForces(self._b, int(flags), stream))
+            self._cf_flags = int(flags)
+            return
+        if active is None or f is None:
+            raise ValueError("update_contact_forces: active and f are given together (%s is missing)" % ("active" if active is None else "f"))
+        pa = _cf_dev_ptr("active", active, "<i4", ((self.B, self.ncand),), self.device)
+        pf = _cf_dev_ptr("f", f, "<f8", ((self.B, self.ncand, 3), (self.B, self.ncand * 3)), self.device)
+        if stream is None and type(f).__module__.split(".")[0] == "torch":
+            import torch
+            stream = torch.cuda.current_stream(f.device).cuda_stream
+        self._chk(self._L.rkfdBatchUpdateContactForcesDev(self._b, int(flags), C.c_void_p(pa), C.c_void_p(pf), C.c_void_p(stream or 0)))
+        self._cf_flags = int(flags)
+        self._ctrl_keep.append((active, f))      # read by a launch that may still be queued
+
+    def get_contact_forces(self):
+        """host copies of the last update_contact_forces(): a dict with (of what its flags selected) point [B, ncand, 3] (world),
+        wrench [B, nlink, 6] (world axes: force, moment about the link origin), count [B, nlink] (int32) and genf [B, ndof]"""
+        if not self._cf_flags:
+            raise RkfdError("get_contact_forces: no contact forces have been computed (update_contact_forces)")
+        out = _cf_arrays(self.B, self.ncand, self.nlink, self.ndof, self._cf_flags)
+        self._chk(self._L.rkfdBatchGetContactForces(self._b, *[_ptr(out.get(k)) for k, _ in _CF_KEYS]))
+        return out
+
+    def contact_force_ptrs(self):
+        """device addresses of point, wrench, count and genf (None for a buffer no update_contact_forces() has needed yet; stable
+        once allocated)"""
+        return tuple(getattr(self._L, f)(self._b) for f in _CF_DEV)
+
+    def contact_force_tensors(self):
+        """the contact read-out's buffers as a dict of zero-copy torch views, point [B, ncand, 3], wrench [B, nlink, 6] and genf
+        [B, ndof] float64, count [B, nlink] int32 (None where no update_contact_forces() has needed the buffer yet, or it is empty)"""
+        import torch
+
+        class _View:
+            def __init__(self, ptr, shape, typestr):
+                self.__cuda_array_interface__ = dict(shape=shape, typestr=typestr, data=(int(ptr), False), version=2, strides=None)
+        shapes = _cf_shapes(self.B, self.ncand, self.nlink, self.ndof)
+        return {k: torch.as_tensor(_View(p, shapes[k], "<i4" if k == "count" else "<f8"), device="cuda") if p and np.prod(shapes[k]) else None
+                for (k, _), p in zip(_CF_KEYS, self.contact_force_ptrs())}
+
     def dev_tensors(self, links=False):
         """torch tensors ALIASING the live device state [B, ndof] (dis, vel, acc): zero-copy views
         for consumers on the device, e.g. the RCCL all-gather of final states.  links=True: the buffers of the task-space
@@ -713,6 +815,7 @@ class Node:
         self.world = world
         m = world.model.contents
         self.total, self.ndof, self.nlink, self.nchain = total, m.ndof, m.nlink, m.nchain
+        self.ncand = m.ncand
         dv = None
         if devices is not None:
             dv = (C.c_int * len(devices))(*devices); ndev = len(devices)
@@ -844,6 +947,13 @@ class Node:
         ns = max(self._L.rkfdBatchJacobianSiteNum(self._L.rkfdNodeBatch(self._n, 0)), 0)
         out = _jac_arrays(self.total, ns, self.nchain, self.ndof, int(flags))
         self._chk(self._L.rkfdNodeGetJacobians(self._n, int(flags), *[_ptr(out.get(k)) for k, _ in _JAC_KEYS]))
+        return out
+
+    def get_contact_forces(self, flags=CF_ALL):
+        """Batch.update_contact_forces(flags) on every device's own thread and stream, then the results of ALL instances in
+        instance order, as Batch.get_contact_forces() returns them"""
+        out = _cf_arrays(self.total, self.ncand, self.nlink, self.ndof, int(flags))
+        self._chk(self._L.rkfdNodeGetContactForces(self._n, int(flags), *[_ptr(out.get(k)) for k, _ in _CF_KEYS]))
         return out
 
     def get_dynamics(self, flags=DYN_ALL):

@@ -20,6 +20,7 @@
 #include "readout/rkfd_links_host.h"   /* the task-space read-out (rkfd_capi_links.hip) */
 #include "readout/rkfd_jac_host.h"     /* the task-space Jacobians (rkfd_capi_jac.hip) */
 #include "readout/rkfd_dyn_host.h"     /* the joint-space dynamics (rkfd_capi_dyn.hip) */
+#include "readout/rkfd_cf_host.h"      /* the contact read-out (rkfd_capi_cf.hip) */
 #include "reset/rkfd_reset_host.h"     /* the per-instance reset and its bank of start states (rkfd_capi_reset.hip) */
 #include "rkfd_device_src.inc"       /* the device headers as string literals (tools/embed_sources.py), for hipRTC */
 
@@ -169,6 +170,9 @@ struct rkfdBatch {
   /* rkfdBatchUpdateDynamics: the joint-space dynamics' tables and result buffers (rkfd_capi_dyn.hip), made by the first launch - a
    * batch that never asks has none */
   rkfdDyn *dyn;
+  /* rkfdBatchUpdateContactForces[Dev]: the contact read-out's tables and result buffers (rkfd_capi_cf.hip), made by the first launch -
+   * a batch that never asks has none */
+  rkfdCf *cf;
   /* rkfdBatchBankReserve / rkfdBatchReset: the bank of start states and the staging of the slot values (rkfd_capi_reset.hip), made by
    * the first of those calls - a batch that never resets one instance alone has none */
   rkfdReset *reset;
@@ -282,6 +286,7 @@ extern "C" void rkfdBatchDestroy(rkfdBatch *b)
   rkfd_links_destroy( b->links );
   rkfd_jac_destroy( b->jac );
   rkfd_dyn_destroy( b->dyn );
+  rkfd_cf_destroy( b->cf );
   rkfd_reset_destroy( b->reset );
   if( b->spec_mod ) (void)hipModuleUnload( b->spec_mod );
   (void)hipFree( b->d_err ); (void)hipFree( b->dblob ); (void)hipFree( b->dblob2 );
@@ -1543,5 +1548,57 @@ extern "C" int rkfdBatchGetDynamics(rkfdBatch *b, double *M, double *h, double *
 extern "C" const double *rkfdBatchDevMassMatrix(rkfdBatch *b){ return b ? rkfd_dyn_dev( b->dyn, 0 ) : NULL; }
 extern "C" const double *rkfdBatchDevBias(rkfdBatch *b){ return b ? rkfd_dyn_dev( b->dyn, 1 ) : NULL; }
 extern "C" const double *rkfdBatchDevGravity(rkfdBatch *b){ return b ? rkfd_dyn_dev( b->dyn, 2 ) : NULL; }
+
+/* ---- contact read-out: candidate positions, link wrenches and the generalised contact force on the device ------ */
+#define CF_FLAG_NAMES "RKFD_CF_POINT, RKFD_CF_WRENCH and RKFD_CF_GENF"
+/* One launch of rkfd_cf_kernel in stream order after everything the batch has launched: the internal split streams are joined onto
+ * `stream` first (as rkfdBatchJoin does), no host wait.  It reads dis and the candidates' flags and forces - the batch's own or the
+ * caller's - and writes the contact read-out's own buffers only. */
+static int cf_launch(rkfdBatch *b, int flags, const int *active, const double *f, void *stream, const char *who)
+{
+  if( flags <= 0 || ( flags & ~( RKFD_CF_POINT | RKFD_CF_WRENCH | RKFD_CF_GENF ) ) ){ SETERR( "%s: flags must be a combination of " CF_FLAG_NAMES " (got %d)", who, flags ); return -1; }
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  char err[400] = "";
+  if( !b->cf ){
+    b->cf = rkfd_cf_create( b->model_for_w2, b->batch, err, sizeof(err) );
+    if( !b->cf ){ SETERR( "%s", err ); return -1; }
+  }
+  if( join_streams( b, (hipStream_t)stream ) < 0 ) return -1;
+  b->last_stream = (hipStream_t)stream; b->launched = 1;
+  if( rkfd_cf_launch( b->cf, b->st.dis, active, f, flags, stream, err, sizeof(err) ) < 0 ){ SETERR( "%s: %s", who, err ); return -1; }
+  return 0;
+}
+extern "C" int rkfdBatchUpdateContactForces(rkfdBatch *b, int flags, void *stream)
+{
+  if( !b ){ SETERR( "rkfdBatchUpdateContactForces: null batch" ); return -1; }
+  return cf_launch( b, flags, b->st.cv_active, b->st.cv_f, stream, "rkfdBatchUpdateContactForces" );
+}
+extern "C" int rkfdBatchUpdateContactForcesDev(rkfdBatch *b, int flags, const int *active_dev, const double *f_dev, void *stream)
+{
+  if( !b ){ SETERR( "rkfdBatchUpdateContactForcesDev: null batch" ); return -1; }
+  if( !active_dev || !f_dev ){ SETERR( "rkfdBatchUpdateContactForcesDev: %s", !active_dev ? "null active_dev" : "null f_dev" ); return -1; }
+  return cf_launch( b, flags, active_dev, f_dev, stream, "rkfdBatchUpdateContactForcesDev" );
+}
+extern "C" int rkfdBatchGetContactForces(rkfdBatch *b, double *point, double *wrench, int *count, double *genf)
+{
+  if( !b ){ SETERR( "rkfdBatchGetContactForces: null batch" ); return -1; }
+  const int have = rkfd_cf_flags( b->cf );
+  if( !have ){ SETERR( "rkfdBatchGetContactForces: no contact forces have been computed (rkfdBatchUpdateContactForces)" ); return -1; }
+  const bool no_p = point && !( have & RKFD_CF_POINT ), no_w = ( wrench || count ) && !( have & RKFD_CF_WRENCH ), no_g = genf && !( have & RKFD_CF_GENF );
+  if( no_p || no_w || no_g ){
+    SETERR( "rkfdBatchGetContactForces: the last rkfdBatchUpdateContactForces (flags %d) did not compute %s", have,
+            no_p ? "the candidate positions (RKFD_CF_POINT)" : no_w ? "the link wrenches and counts (RKFD_CF_WRENCH)" : "the generalised contact force (RKFD_CF_GENF)" );
+    return -1;
+  }
+  if( !point && !wrench && !count && !genf ) return 0;
+  HIPCHK( hipSetDevice( b->device ), -1 );
+  char err[400] = "";
+  if( rkfd_cf_get( b->cf, point, wrench, count, genf, err, sizeof(err) ) < 0 ){ SETERR( "rkfdBatchGetContactForces: %s", err ); return -1; }
+  return 0;
+}
+extern "C" const double *rkfdBatchDevContactPoint(rkfdBatch *b){ return b ? (const double *)rkfd_cf_dev( b->cf, 0 ) : NULL; }
+extern "C" const double *rkfdBatchDevContactWrench(rkfdBatch *b){ return b ? (const double *)rkfd_cf_dev( b->cf, 1 ) : NULL; }
+extern "C" const int *rkfdBatchDevContactCount(rkfdBatch *b){ return b ? (const int *)rkfd_cf_dev( b->cf, 2 ) : NULL; }
+extern "C" const double *rkfdBatchDevContactGenForce(rkfdBatch *b){ return b ? (const double *)rkfd_cf_dev( b->cf, 3 ) : NULL; }
 
 #include "rkfd_capi_node.inc"      /* the node level: one host thread + stream per device, one RCCL all-gather of final states */

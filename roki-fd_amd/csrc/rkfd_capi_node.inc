@@ -48,7 +48,7 @@ static const rkfdRccl *rccl_api(void)
   return state == 1 ? &api : NULL;
 }
 
-enum { NODE_CMD_NONE = 0, NODE_CMD_INIT, NODE_CMD_UPDATE, NODE_CMD_SPECIALIZE, NODE_CMD_SPLIT, NODE_CMD_STEPS_PER_LAUNCH, NODE_CMD_TUNE, NODE_CMD_STATUS, NODE_CMD_SNAPSHOT, NODE_CMD_RESTORE, NODE_CMD_PACK, NODE_CMD_UPDATE_CTRL, NODE_CMD_LINKS, NODE_CMD_RESET, NODE_CMD_JAC, NODE_CMD_DYN, NODE_CMD_QUIT };
+enum { NODE_CMD_NONE = 0, NODE_CMD_INIT, NODE_CMD_UPDATE, NODE_CMD_SPECIALIZE, NODE_CMD_SPLIT, NODE_CMD_STEPS_PER_LAUNCH, NODE_CMD_TUNE, NODE_CMD_STATUS, NODE_CMD_SNAPSHOT, NODE_CMD_RESTORE, NODE_CMD_PACK, NODE_CMD_UPDATE_CTRL, NODE_CMD_LINKS, NODE_CMD_RESET, NODE_CMD_JAC, NODE_CMD_DYN, NODE_CMD_CF, NODE_CMD_QUIT };
 
 struct rkfdNode;
 struct rkfdNodeWorker {
@@ -86,6 +86,7 @@ static int node_run_on(rkfdNode *n, int k, int cmd, int arg)
   case NODE_CMD_LINKS:      return rkfdBatchUpdateLinks( b, arg, n->st[k] );
   case NODE_CMD_JAC:        return rkfdBatchUpdateJacobians( b, arg, n->st[k] );
   case NODE_CMD_DYN:        return rkfdBatchUpdateDynamics( b, arg, n->st[k] );
+  case NODE_CMD_CF:         return rkfdBatchUpdateContactForces( b, arg, n->st[k] );
   case NODE_CMD_RESET:      return reset_launch( b, NULL, n->st[k], "rkfdNodeReset" );      /* (rkfdNodeReset has staged the shard's slot values) */
   case NODE_CMD_SPECIALIZE: return rkfdBatchSpecialize( b );
   case NODE_CMD_SPLIT:      return rkfdBatchSetSplit( b, arg );
@@ -379,6 +380,19 @@ extern "C" int rkfdNodeGetDynamics(rkfdNode *n, int flags, double *M, double *h,
   for( int k=0; k<n->ndev; k++ ){
     const size_t lo = (size_t)n->lo[k], nd = (size_t)n->ndof;
     if( rkfdBatchGetDynamics( n->b[k], M ? M + lo*nd*nd : NULL, h ? h + lo*nd : NULL, g ? g + lo*nd : NULL ) < 0 ) return -1;
+  }
+  return 0;
+}
+/* rkfdBatchUpdateContactForces( flags ) on every device's own thread and stream, then the host arrays in instance order (the
+ * pointer of a quantity `flags` does not select must be NULL) */
+extern "C" int rkfdNodeGetContactForces(rkfdNode *n, int flags, double *point, double *wrench, int *count, double *genf)
+{
+  if( !n ){ SETERR( "rkfdNodeGetContactForces: null node" ); return -1; }
+  if( node_all( n, NODE_CMD_CF, flags ) < 0 ) return -1;
+  for( int k=0; k<n->ndev; k++ ){
+    const size_t lo = (size_t)n->lo[k], nd = (size_t)n->ndof, nl = (size_t)n->nlink, nc = (size_t)n->ncand;
+    if( rkfdBatchGetContactForces( n->b[k], point ? point + lo*nc*3 : NULL, wrench ? wrench + lo*nl*6 : NULL, count ? count + lo*nl : NULL,
+                                   genf ? genf + lo*nd : NULL ) < 0 ) return -1;
   }
   return 0;
 }
