@@ -82,7 +82,7 @@ spec: $(LIB)
 
 emu: tests/emu/librkfd_emu.so tests/emu/librkfd_emu_w2.so tests/emu/librkfd_emu_ctrl.so tests/emu/librkfd_emu_ctrl_w2.so \
      tests/emu/librkfd_emu_par.so tests/emu/librkfd_emu_par_w2.so tests/emu/librkfd_emu_links.so tests/emu/librkfd_emu_reset.so \
-     tests/emu/librkfd_emu_jac.so tests/emu/librkfd_emu_dyn.so tests/emu/librkfd_emu_cf.so
+     tests/emu/librkfd_emu_jac.so tests/emu/librkfd_emu_dyn.so tests/emu/librkfd_emu_cf.so tests/emu/librkfd_emu_prim.so
 
 tests/emu/librkfd_emu.so: tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_device.h $(CSRC)/rkfd_devmodel.cpp $(CSRC)/*.h $(CSRC)/device/*.h include/*.h
 	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread $(INC) -o $@ tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_devmodel.cpp
@@ -121,12 +121,16 @@ tests/emu/librkfd_emu_dyn.so: tests/emu/rkfd_emu_dyn.cpp tests/emu/rkfd_emu.cpp 
 tests/emu/librkfd_emu_cf.so: tests/emu/rkfd_emu_cf.cpp tests/emu/rkfd_emu.cpp $(CSRC)/readout/*.h $(CSRC)/rkfd_device.h $(CSRC)/rkfd_devmodel.cpp $(CSRC)/*.h $(CSRC)/device/*.h include/*.h
 	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread $(INC) -o $@ tests/emu/rkfd_emu_cf.cpp $(CSRC)/rkfd_devmodel.cpp
 
+# the rotation primitives of device/rkfd_dev_base.h (d_sincos, d_atan2_ypos, d_from_aa, d_to_aa) as plain loops
+tests/emu/librkfd_emu_prim.so: tests/emu/rkfd_emu_prim.cpp tests/emu/rkfd_emu.cpp $(CSRC)/rkfd_device.h $(CSRC)/rkfd_devmodel.cpp $(CSRC)/*.h $(CSRC)/device/*.h include/*.h
+	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread $(INC) -o $@ tests/emu/rkfd_emu_prim.cpp $(CSRC)/rkfd_devmodel.cpp
+
 # the harness of the per-instance reset (reset/rkfd_reset.h, the device code of rkfdBatchReset)
 tests/emu/librkfd_emu_reset.so: tests/emu/rkfd_emu_reset.cpp $(CSRC)/reset/rkfd_reset.h $(CSRC)/rkfd_devmodel.h include/*.h
 	$(CXX) -std=c++20 -O2 -Wall -Wno-unknown-pragmas -fPIC -shared -pthread $(INC) -o $@ tests/emu/rkfd_emu_reset.cpp
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(PKG)/spec $(PKG)/kernel_resources_links.txt tests/emu/librkfd_emu_links.so $(PKG)/kernel_resources_reset.txt tests/emu/librkfd_emu_reset.so $(PKG)/kernel_resources_jac.txt tests/emu/librkfd_emu_jac.so $(PKG)/kernel_resources_dyn.txt tests/emu/librkfd_emu_dyn.so $(PKG)/kernel_resources_cf.txt tests/emu/librkfd_emu_cf.so tests/emu/librkfd_emu.so tests/emu/librkfd_emu_w2.so tests/emu/librkfd_emu_ctrl.so tests/emu/librkfd_emu_ctrl_w2.so tests/emu/librkfd_emu_par.so tests/emu/librkfd_emu_par_w2.so
+	rm -rf $(BUILD) $(LIB) $(PKG)/spec $(PKG)/kernel_resources_links.txt tests/emu/librkfd_emu_links.so $(PKG)/kernel_resources_reset.txt tests/emu/librkfd_emu_reset.so $(PKG)/kernel_resources_jac.txt tests/emu/librkfd_emu_jac.so $(PKG)/kernel_resources_dyn.txt tests/emu/librkfd_emu_dyn.so $(PKG)/kernel_resources_cf.txt tests/emu/librkfd_emu_cf.so tests/emu/librkfd_emu_prim.so tests/emu/librkfd_emu.so tests/emu/librkfd_emu_w2.so tests/emu/librkfd_emu_ctrl.so tests/emu/librkfd_emu_ctrl_w2.so tests/emu/librkfd_emu_par.so tests/emu/librkfd_emu_par_w2.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle emu spec clean
